@@ -18,8 +18,25 @@ replay (instantiation), untimed replays until --settle-ms of GPU time has
 passed (the device's clock ramp under sustained load),
 then ONE timed replay of exactly K steps between barriers and synchronises.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: it
+sets up, warms up, settles, times the K steps, checks their round trip,
+writes --dump-outputs and prints the headline line (metric, value, unit,
+ms_per_step, settle, timed_split, config, build).  Everything below that is
+marked --full runs only with that option, after the timed replay (the
+per-kernel replays of graph_shares just before it).
+
+--dump-outputs DIR writes what the last timed step returned to its caller as
+float32 DIR/<name>.npy (rank r > 0: <name>.rank<r>.npy): a seeded sample of
+whole frames (sampled_frames: their indices) with each one's wire frame
+(wire) and decoded payload (payload), and every frame's decoded flags and
+status.  The encoder's send counter is then set to DUMP_NONCE after the
+settling (one more untimed pass of the K steps follows), so the wire does not
+depend on how many settling replays the clock took: the same arguments give
+the same arrays from run to run.
+
 JSON line fields beyond the driver contract:
   settle        the untimed settling replays' time per step, in order
+The fields below: --full only.
   roofline      dominant kernel (decode frame kernel) achieved algorithmic HBM-read
                 GB/s vs the 8 TB/s peak.  HIP events cannot time a kernel
                 inside a replayed graph, so the per-launch durations come
@@ -60,6 +77,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md chip table (spec)
 ROOF_KERNEL = "k_frames_seq<decode>"  # the dominant kernel of the bench workload (one lane per frame)
+DUMP_NONCE = 1 << 48  # --dump-outputs: the send counter at the first timed step (above any the settling reaches)
+DUMP_ELEMS = 6_000_000  # --dump-outputs: float32 elements per sampled array (4 arrays: under 64 MB in all)
 
 
 def parse():
@@ -69,6 +88,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--msgs", type=int, default=65536)
     p.add_argument("--size", type=int, default=1024)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also measure everything else: per-kernel durations and roofline, the "
+                        "eager passes, hbm_fed, the other BASELINE configs, host_paths and cpu_baseline (the "
+                        "options below that shape or skip those parts act only with --full)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the last timed step's outputs (a seeded sample of whole frames) as DIR/<name>.npy")
     p.add_argument("--settle-ms", type=float, default=40.0,
                    help="untimed replays of the captured steps before the timed one, until this much GPU time "
                         "has passed (the clock ramp under sustained load; 0: none)")
@@ -148,9 +173,15 @@ def main():
     n_devices, shared_devices = device_census(torch, world, local)
 
     from libzmq_amd import curve as C
+    from libzmq_amd import shard
 
     n, P = args.msgs, args.size
     W = C.wire_size(0, 0, P)
+    dump_idx = None
+    if args.dump_outputs:  # the sampled frames, fixed by the arguments alone
+        m = max(1, min(n, DUMP_ELEMS // W))
+        dump_idx = np.sort(np.random.default_rng(0xD0).choice(n, m, replace=False)).astype(np.int64)
+        dump_idx = torch.from_numpy(dump_idx).to(dev)
     g = torch.Generator(device=dev)
     g.manual_seed(0x5EED + rank)
     payload = torch.randint(0, 256, (n * P,), dtype=torch.uint8, device=dev, generator=g)
@@ -203,13 +234,13 @@ def main():
     # The K timed steps are captured once as a hipGraph (the kernels' per-call
     # state lives on the device, so replays are exact) and replayed as one
     # launch: the host's per-kernel launch cost stays out of the timed region.
-    # HIP events cannot time kernels inside a graph, so the per-launch kernel
-    # durations (roofline) come from graph replays just before the timed one
-    # (graph_shares).  An eager pass of K more steps right after the timed
-    # replay gives eager_ms_per_step (host-launched calls, hooks off), and a
-    # second one with the ctx profiling hooks on the call spans
-    # (roofline.hooked_eager).  --eager times the eager steps (events on)
-    # instead.
+    # With --full: HIP events cannot time kernels inside a graph, so the
+    # per-launch kernel durations (roofline) come from graph replays just
+    # before the timed one (graph_shares); an eager pass of K more steps right
+    # after the timed replay gives eager_ms_per_step (host-launched calls,
+    # hooks off), and a second one with the ctx profiling hooks on the call
+    # spans (roofline.hooked_eager).  --eager times the eager steps instead
+    # (with --full, events on).
     graph = None
     if not args.eager:
         try:
@@ -246,13 +277,24 @@ def main():
         ms = s0.elapsed_time(s1)
         settle_t += ms
         settle_us.append(round(1e3 * ms / args.steps, 1))
+    # --dump-outputs: the wire must not depend on how many settling replays the
+    # clock took, so the send counter restarts at a fixed value here; the host
+    # call idles the device, so one more untimed pass of the K steps follows
+    if dump_idx is not None:
+        enc.set_nonce(0, DUMP_NONCE)
+        if graph is not None:
+            graph.replay()
+        else:
+            for _ in range(args.steps):
+                step(stream)
+        torch.cuda.synchronize(dev)
     # The frame kernels' per-launch durations at the timed replay's clock:
     # replays alternating with an encode-only graph, between the settling and
     # the timed replay (the device ramps down within milliseconds of idling,
     # so after the timed replay's checks they would measure another clock).
-    if graph is not None:
+    if args.full and graph is not None:
         enc_avg_s, dec_avg_s, shares = graph_shares(torch, dev, stream, graph, step_enc, args.steps)
-    if graph is None:
+    if args.full and graph is None:
         enc.set_profiling(True)
         dec.set_profiling(True)
     if world > 1:
@@ -277,6 +319,59 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = t1 - t0
+    # --dump-outputs: the sampled frames of the last timed step, gathered on the
+    # device behind the timed steps (--full's eager passes reuse the buffers)
+    dump = None
+    if dump_idx is not None:
+        dump = {"sampled_frames": dump_idx, "wire": wire.view(n, W).index_select(0, dump_idx),
+                "payload": back.view(n, P).index_select(0, dump_idx), "flags": fl_out.index_select(0, dump_idx),
+                "status": st_out.index_select(0, dump_idx)}
+
+    def headline(elapsed):
+        """The result line of a plain run (and the head of --full's)."""
+        total_msgs = n * args.steps * world
+        src_id, commit = C.build_id()
+        return {
+            "metric": "GiB/s device-resident CURVE encode+decode, 1 KiB-msg batches; msgs/s",
+            "value": total_msgs * P / 2**30 / elapsed,
+            "unit": "GiB/s",
+            "msgs_per_s": total_msgs / elapsed,
+            "n_gpus": n_devices,
+            "ranks": world,
+            "shared_devices": shared_devices,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32",
+            "data": "synthetic (seeded random payload bytes, random precomputed key)",
+            "launch": "hipGraph replay of the K captured steps" if graph is not None else "eager host launches",
+            "timed_split": timed_split,
+            "settle": {"gpu_ms": settle_t, "replays_us_per_step": settle_us},
+            "config": {"workload": f"config2: {n} x {P} B frames, 1 CURVE session per GPU, encode+decode round trip",
+                       "frames_per_gpu": n, "payload_bytes": P, "wire_bytes": W, "sessions": 1,
+                       "parallelism": f"frame-sharded x{world}, no collective"},
+            "build": {"source_id": src_id, "commit": commit},
+        }
+
+    def finish(result):
+        if dump is not None:
+            write_outputs(args.dump_outputs, dump, rank)
+            result["dump_outputs"] = {"dir": args.dump_outputs, "frames": int(dump_idx.numel()),
+                                      "nonce_after_settling": DUMP_NONCE}
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run: the timed steps' results checked, the headline, nothing else
+        assert int((st_out != 0).sum()) == 0 and torch.equal(back, payload), "timed steps: round trip mismatch"
+        finish(headline(shard.max_over_ranks(elapsed)))
+        return
+
     eager_elapsed = None
     if graph is not None:
         # the same K steps launched from the host call by call (what a caller
@@ -296,7 +391,6 @@ def main():
         for _ in range(args.steps):
             step(stream)
         torch.cuda.synchronize(dev)
-    from libzmq_amd import shard
     elapsed = shard.max_over_ranks(elapsed)  # the slowest rank times the job
     # the eager pass's event pairs (the hooks were off during the capture)
     enc_body_ms, enc_body_n = enc.get_profile(C.CurveContext.PROF_ENCODE_MAIN)
@@ -326,11 +420,6 @@ def main():
     if args.hbm_sets > 0:
         hbm = hbm_fed(torch, dev, stream, enc, dec, args.hbm_sets, n, W, P, sid, flags, in_off, lens, out_off, wlen,
                       payload)
-
-    total_msgs = n * args.steps * world
-    gib = total_msgs * P / 2**30
-    value = gib / elapsed
-    ms_per_step = 1e3 * elapsed / args.steps
 
     # roofline of the dominant kernel: the decode frame kernel.  Algorithmic HBM-read
     # bytes of decode per frame: wire W + sid 4 + offset 8 +
@@ -409,33 +498,13 @@ def main():
                 "path_read_frac": (n * (2 * P + 74)) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS * world
                 if world == 1 else None}
 
-    result = {
-        "metric": "GiB/s device-resident CURVE encode+decode, 1 KiB-msg batches; msgs/s",
-        "value": value,
-        "unit": "GiB/s",
-        "msgs_per_s": total_msgs / elapsed,
-        "n_gpus": n_devices,
-        "ranks": world,
-        "shared_devices": shared_devices,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (seeded random payload bytes, random precomputed key)",
-        "launch": "hipGraph replay of the K captured steps" if graph is not None else "eager host launches",
+    result = headline(elapsed)
+    result.update({
+        "full": True,
         "eager_ms_per_step": 1e3 * (eager_elapsed if eager_elapsed is not None else elapsed) / args.steps,
-        "timed_split": timed_split,
-        "settle": {"gpu_ms": settle_t, "replays_us_per_step": settle_us},
-        "config": {"workload": f"config2: {n} x {P} B frames, 1 CURVE session per GPU, encode+decode round trip",
-                   "frames_per_gpu": n, "payload_bytes": P, "wire_bytes": W, "sessions": 1,
-                   "parallelism": f"frame-sharded x{world}, no collective"},
         "roofline": roofline,
         "hbm_fed": hbm,
-        "build": {"source_id": src_id, "commit": commit},
-    }
+    })
 
     if not args.no_configs:
         result["configs"] = other_configs(C, torch, dev, local, rank, world, args.configs.split(","),
@@ -456,11 +525,17 @@ def main():
         else:
             result["cpu_baseline"] = port
 
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(result)
+
+
+def write_outputs(path, arrays, rank):
+    """--dump-outputs: each array as float32 <path>/<name>.npy (rank r > 0:
+    <name>.rank<r>.npy); bytes, flags, statuses and frame indices are all
+    exact in float32."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(path, name + (".npy" if rank == 0 else f".rank{rank}.npy")), a)
 
 
 def graph_shares(torch, dev, stream, graph, step_enc, K, reps=5):

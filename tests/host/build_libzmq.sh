@@ -111,8 +111,10 @@ variant stock "" libzmq_test_switches.patch
 link stock
 # the CPU baseline on the stock build's own curve_encoding_t (bench.py)
 # (libsodium through a directory of its own: an rpath to $SODIUM/lib would
-# also pick that tree's older libstdc++ for the program)
-mkdir -p "$OUT/sodium" && ln -sf "$SODIUM/lib/libsodium.so.23" "$OUT/sodium/libsodium.so.23"
+# also pick that tree's older libstdc++ for the program; a copy, not a link:
+# the build adds no links under tests/)
+mkdir -p "$OUT/sodium" && rm -f "$OUT/sodium/libsodium.so.23" \
+  && cp -L "$SODIUM/lib/libsodium.so.23" "$OUT/sodium/libsodium.so.23"
 g++ $CXXFLAGS $inc -o "$OUT/curve_encoding_ref_bench" "$HERE/curve_encoding_ref_bench.cpp" \
   "$OUT/stock/libzmq.so.5" "$OUT/sodium/libsodium.so.23" -Wl,-rpath,'$ORIGIN/stock:$ORIGIN/sodium' -lpthread
 

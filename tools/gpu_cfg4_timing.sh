@@ -8,7 +8,7 @@ for r in 1 2 3; do
   O=gpurun_out/cfg4t/r$r
   mkdir -p $O
   timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $PWD/$O -o c4 -- \
-      python3 bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-host-staged --no-deployable --hbm-sets 0 \
+      python3 bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-host-staged --no-deployable --hbm-sets 0 \
       --configs 4 > $O/bench.json 2> $O/run.err || { tail -5 $O/run.err; exit 1; }
   python3 - "$O/c4_kernel_stats.csv" <<'PY'
 import csv, sys

@@ -1,15 +1,16 @@
 #!/bin/bash
-# Full GPU test suite, then a default bench run (log under gpurun_out/chk).
+# Full GPU test suite, then a default bench run (log under $OUT/chk).
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out/chk
-timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/chk/pytest.log 2>&1 || { tail -40 gpurun_out/chk/pytest.log; exit 1; }
-tail -1 gpurun_out/chk/pytest.log
-timeout -k 10 400 python bench.py > gpurun_out/chk/bench.log 2>&1 || { tail -20 gpurun_out/chk/bench.log; exit 1; }
-tail -1 gpurun_out/chk/bench.log > gpurun_out/chk/bench.json
-python3 - <<'PY'
-import json
-d = json.load(open("gpurun_out/chk/bench.json"))
+OUT=${OUT:-out}  # where logs and results go
+mkdir -p $OUT/chk
+timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $OUT/chk/pytest.log 2>&1 || { tail -40 $OUT/chk/pytest.log; exit 1; }
+tail -1 $OUT/chk/pytest.log
+timeout -k 10 400 python bench.py --full > $OUT/chk/bench.log 2>&1 || { tail -20 $OUT/chk/bench.log; exit 1; }
+tail -1 $OUT/chk/bench.log > $OUT/chk/bench.json
+python3 - "$OUT/chk/bench.json" <<'PY'
+import json, sys
+d = json.load(open(sys.argv[1]))
 h = d["hbm_fed"]
 print("main", round(d["value"], 1), "dec_us", round(d["roofline"]["avg_launch_us"], 1), "frac", round(d["roofline"]["frac"], 3))
 print("hbm", round(h["value"], 1), "enc", round(h["encode_us"], 1), "dec", round(h["decode_us"], 1))

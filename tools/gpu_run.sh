@@ -30,7 +30,8 @@
 # Every GPU step runs under its own time limit and the script stops at the
 # first failure.
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+OUT=${OUT:-out}  # where logs and results go
+mkdir -p $OUT
 export TMPDIR=/tmp
 MODE=${1:-suite}
 shift
@@ -39,26 +40,26 @@ kb() { timeout -k 10 180 python -u tools/kbench.py "$@"; }
 
 case $MODE in
 suite)
-  timeout -k 10 1000 $PYTEST tests -m gpu > gpurun_out/pytest_gpu.log 2>&1
-  rc=$?; grep -E "passed|failed|error" gpurun_out/pytest_gpu.log | tail -3
-  if [ $rc -ne 0 ]; then grep -B5 -A30 "FAILED\|Error" gpurun_out/pytest_gpu.log | head -80; exit 1; fi
+  timeout -k 10 1000 $PYTEST tests -m gpu > $OUT/pytest_gpu.log 2>&1
+  rc=$?; grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -3
+  if [ $rc -ne 0 ]; then grep -B5 -A30 "FAILED\|Error" $OUT/pytest_gpu.log | head -80; exit 1; fi
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
   ;;
 bench)
-  timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > gpurun_out/bench.json 2> gpurun_out/bench.err \
-    || { tail -20 gpurun_out/bench.err; exit 1; }
-  tail -1 gpurun_out/bench.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'], d['roofline']['pmc_files'], {k: round(v['value'],1) for k,v in d.get('configs',{}).items()})"
+  timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err \
+    || { tail -20 $OUT/bench.err; exit 1; }
+  tail -1 $OUT/bench.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'], d['roofline']['pmc_files'], {k: round(v['value'],1) for k,v in d.get('configs',{}).items()})"
   ;;
 prof)
   TAG=${1:-rNN}
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $PWD/gpurun_out/prof_c2 -o c2 --output-format csv -- \
-      python3 bench.py --steps 20 --warmup 5 --no-configs --no-host-staged --no-cpu-baseline \
-      > gpurun_out/prof_c2.json 2> gpurun_out/prof_c2.err || { tail -20 gpurun_out/prof_c2.err; exit 1; }
-  tail -1 gpurun_out/prof_c2.json
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $PWD/gpurun_out/prof_all -o all --output-format csv -- \
-      python3 bench.py --steps 20 --warmup 5 --no-host-staged --no-cpu-baseline \
-      > gpurun_out/prof_all.json 2> gpurun_out/prof_all.err || { tail -20 gpurun_out/prof_all.err; exit 1; }
-  find gpurun_out/prof_c2 gpurun_out/prof_all -name "*kernel_stats.csv"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $PWD/$OUT/prof_c2 -o c2 --output-format csv -- \
+      python3 bench.py --full --steps 20 --warmup 5 --no-configs --no-host-staged --no-cpu-baseline \
+      > $OUT/prof_c2.json 2> $OUT/prof_c2.err || { tail -20 $OUT/prof_c2.err; exit 1; }
+  tail -1 $OUT/prof_c2.json
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $PWD/$OUT/prof_all -o all --output-format csv -- \
+      python3 bench.py --full --steps 20 --warmup 5 --no-host-staged --no-cpu-baseline \
+      > $OUT/prof_all.json 2> $OUT/prof_all.err || { tail -20 $OUT/prof_all.err; exit 1; }
+  find $OUT/prof_c2 $OUT/prof_all -name "*kernel_stats.csv"
   ;;
 pmc)
   bash tools/pmc_profiles.sh || exit 1
@@ -67,8 +68,8 @@ ab)
   A=$1; shift
   for r in 1 2 3; do
     for lib in $A libzmq_amd/libzmqg_curve.so; do
-      ZMQG_CURVE_LIB=$PWD/$lib kb --tag $lib "$@" > gpurun_out/ab.log 2>&1 || { tail -20 gpurun_out/ab.log; exit 1; }
-      tail -1 gpurun_out/ab.log
+      ZMQG_CURVE_LIB=$PWD/$lib kb --tag $lib "$@" > $OUT/ab.log 2>&1 || { tail -20 $OUT/ab.log; exit 1; }
+      tail -1 $OUT/ab.log
     done
   done
   ;;
@@ -76,37 +77,37 @@ benchab)
   A=$1
   for r in 1 2; do
     for lib in $A libzmq_amd/libzmqg_curve.so; do
-      ZMQG_CURVE_LIB=$PWD/$lib timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline \
-          --no-host-staged --no-configs > gpurun_out/benchab.json 2> gpurun_out/benchab.err \
-          || { tail -20 gpurun_out/benchab.err; exit 1; }
-      tail -1 gpurun_out/benchab.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', round(d['value'],1), round(d['ms_per_step']*1000,1), round(d['roofline']['avg_launch_us'],1), round(d['roofline']['encode_main_avg_us'],1))"
+      ZMQG_CURVE_LIB=$PWD/$lib timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline \
+          --no-host-staged --no-configs > $OUT/benchab.json 2> $OUT/benchab.err \
+          || { tail -20 $OUT/benchab.err; exit 1; }
+      tail -1 $OUT/benchab.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', round(d['value'],1), round(d['ms_per_step']*1000,1), round(d['roofline']['avg_launch_us'],1), round(d['roofline']['encode_main_avg_us'],1))"
     done
   done
   ;;
 zmtp)
-  timeout -k 10 300 $PYTEST tests/test_zmtp.py -m gpu > gpurun_out/pytest_zmtp.log 2>&1 \
-    || { tail -40 gpurun_out/pytest_zmtp.log; exit 1; }
-  tail -1 gpurun_out/pytest_zmtp.log
+  timeout -k 10 300 $PYTEST tests/test_zmtp.py -m gpu > $OUT/pytest_zmtp.log 2>&1 \
+    || { tail -40 $OUT/pytest_zmtp.log; exit 1; }
+  tail -1 $OUT/pytest_zmtp.log
   for r in 1 2; do
     timeout -k 10 180 python -u tools/zmtp_bench.py || exit 1
   done
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $PWD/gpurun_out/zprof -o run --output-format csv -- \
-      python -u tools/zmtp_bench.py > gpurun_out/zprof.log 2>&1 || { tail -20 gpurun_out/zprof.log; exit 1; }
-  find gpurun_out/zprof -name "*kernel_trace.csv" -delete
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $PWD/$OUT/zprof -o run --output-format csv -- \
+      python -u tools/zmtp_bench.py > $OUT/zprof.log 2>&1 || { tail -20 $OUT/zprof.log; exit 1; }
+  find $OUT/zprof -name "*kernel_trace.csv" -delete
   ;;
 msg)
-  timeout -k 10 300 $PYTEST tests/test_gpu_msg.py tests/test_host_adapter.py -m gpu > gpurun_out/pytest_msg.log 2>&1 \
-    || { tail -30 gpurun_out/pytest_msg.log; exit 1; }
-  tail -1 gpurun_out/pytest_msg.log
+  timeout -k 10 300 $PYTEST tests/test_gpu_msg.py tests/test_host_adapter.py -m gpu > $OUT/pytest_msg.log 2>&1 \
+    || { tail -30 $OUT/pytest_msg.log; exit 1; }
+  tail -1 $OUT/pytest_msg.log
   LD_LIBRARY_PATH=$PWD/libzmq_amd:$LD_LIBRARY_PATH timeout -k 10 120 ./tools/bin/msg_kernel_bench tree || exit 1
-  timeout -k 10 120 ./tools/bin/msg_latency > gpurun_out/msg_latency.json 2>&1 || exit 1
-  grep '^{' gpurun_out/msg_latency.json
+  timeout -k 10 120 ./tools/bin/msg_latency > $OUT/msg_latency.json 2>&1 || exit 1
+  grep '^{' $OUT/msg_latency.json
   ;;
 cfg4)
   for r in 1 2; do
     for g in default 0 8; do
       if [ $g = default ]; then unset ZMQG_FRAMES_G; else export ZMQG_FRAMES_G=$g; fi
-      timeout -k 10 300 python bench.py --steps 5 --warmup 2 --configs 4 --no-cpu-baseline --no-host-staged 2>/dev/null \
+      timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --configs 4 --no-cpu-baseline --no-host-staged 2>/dev/null \
         | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['configs']['config4']; print('G=$g', 'config4', round(c['value'],1), 'GiB/s', round(c['ms_per_step'],3), 'ms/step')" || exit 1
     done
   done
@@ -121,10 +122,10 @@ twowave)
   ;;
 engine)
   timeout -k 10 600 $PYTEST -s tests/test_host_adapter.py tests/test_gpu_notify.py tests/test_libzmq_interop.py \
-      > gpurun_out/pytest_engine.log 2>&1
-  rc=$?; tail -3 gpurun_out/pytest_engine.log
-  if [ $rc -ne 0 ]; then grep -B5 -A30 "FAILED\|Error" gpurun_out/pytest_engine.log | head -60; exit 1; fi
-  grep -E "^OK 4800|'msgs_per_s'" gpurun_out/pytest_engine.log || true
+      > $OUT/pytest_engine.log 2>&1
+  rc=$?; tail -3 $OUT/pytest_engine.log
+  if [ $rc -ne 0 ]; then grep -B5 -A30 "FAILED\|Error" $OUT/pytest_engine.log | head -60; exit 1; fi
+  grep -E "^OK 4800|'msgs_per_s'" $OUT/pytest_engine.log || true
   ;;
 sweep)
   for r in 1 2; do
@@ -135,7 +136,7 @@ sweep)
   done
   ;;
 pmc4)
-  O=gpurun_out/pmc4
+  O=$OUT/pmc4
   mkdir -p $O
   timeout -k 10 60 rocprofv3 --list-avail > $O/counters.txt 2>&1 || true
   p=0
@@ -155,7 +156,7 @@ pmc4)
 pmc4b)
   # config 4: the store ablations' counters, and VALU per frame against the
   # frame's window count (k_frames_lds forced) for the fixed per-frame part
-  O=gpurun_out/pmc4b
+  O=$OUT/pmc4b
   mkdir -p $O
   C="SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAVES"
   for L in default abl512 abl1024 abl1536; do
@@ -169,7 +170,7 @@ pmc4b)
         python tools/kbench.py --msgs 1048576 --size $P --sessions 1024 --sid-mod --iters 2 > $O/sz$P.log 2>&1 \
         || { echo "pmc4b size $P failed"; tail -5 $O/sz$P.log; exit 1; }
   done
-  # (only the counter summaries come back: gpurun_out is capped)
+  # (only the counter summaries come back: the output folder is capped)
   find $O -name "*kernel_trace.csv" -delete
   find $O -name "*agent_info.csv" -delete
   ;;
@@ -187,10 +188,10 @@ hookbench)
   done
   ;;
 interop)
-  timeout -k 10 600 $PYTEST -s tests/test_libzmq_interop.py > gpurun_out/pytest_interop.log 2>&1
-  rc=$?; tail -3 gpurun_out/pytest_interop.log
-  if [ $rc -ne 0 ]; then grep -B5 -A30 "FAILED\|Error" gpurun_out/pytest_interop.log | head -60; exit 1; fi
-  grep -E "'msgs_per_s'|'gamma'" gpurun_out/pytest_interop.log || true
+  timeout -k 10 600 $PYTEST -s tests/test_libzmq_interop.py > $OUT/pytest_interop.log 2>&1
+  rc=$?; tail -3 $OUT/pytest_interop.log
+  if [ $rc -ne 0 ]; then grep -B5 -A30 "FAILED\|Error" $OUT/pytest_interop.log | head -60; exit 1; fi
+  grep -E "'msgs_per_s'|'gamma'" $OUT/pytest_interop.log || true
   ;;
 settle)
   timeout -k 10 180 python -u tools/replay_series.py --reps 60 || exit 1

@@ -13,7 +13,7 @@ for C in "$A" "FETCH_SIZE" "WRITE_SIZE"; do
   O=gpurun_out/pmc4/p$p
   mkdir -p $O
   timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $PWD/$O -o pmc -- \
-      python bench.py --steps 1 --warmup 1 --settle-ms 0 --no-cpu-baseline --no-host-staged --no-deployable \
+      python bench.py --full --steps 1 --warmup 1 --settle-ms 0 --no-cpu-baseline --no-host-staged --no-deployable \
       --hbm-sets 0 --configs 4 > $O/run.log 2>&1 || { echo "pmc pass $p failed"; tail -5 $O/run.log; exit 1; }
 done
 python tools/pmc_summary.py gpurun_out/pmc4 16777216 256 gpurun_out/pmc4/summary.json "config 4: 16 Mi x 256 B, 1024 sessions, k_frames_lds"

@@ -13,7 +13,7 @@ for c in ${CFGS:-3 4 5}; do
     O=gpurun_out/pmcc/c$c/p$p
     mkdir -p $O
     timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $PWD/$O -o pmc -- \
-        python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-host-staged --configs $c > $O/run.log 2>&1 \
+        python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-host-staged --configs $c > $O/run.log 2>&1 \
         || { echo "pmc config $c pass $p failed"; tail -5 $O/run.log; exit 1; }
   done
 done

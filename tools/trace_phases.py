@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Frame-kernel durations of one bench.py run by phase, from a rocprofv3
+"""Frame-kernel durations of one bench.py --full run by phase, from a rocprofv3
 kernel trace of it (tools/gpu_run.sh prof writes one): the runs of 2K
 back-to-back frame launches (graph replays: gaps under 20 us) in order --
 the untimed instantiation and settling replays, then the timed replay --
