@@ -38,7 +38,7 @@
 #pragma once
 
 #ifndef ZMQG_FRAMES_ABLATE
-#define ZMQG_FRAMES_ABLATE 0 // timing/counting experiments only: k_frames: 1 no Poly1305, 2 no stores, 4 no input shift; k_frames_seq: 8 no stores, 16 no loads, 32 no Salsa20, 64 no Poly1305, 128 stores to 64-byte-aligned places (whole lines), 256 loads from 64-byte-aligned places; k_frames_lds: 512 no partial edge granules, 1024 the encode head as two aligned dwordx4
+#define ZMQG_FRAMES_ABLATE 0 // timing/counting experiments only: k_frames: 1 no Poly1305, 2 no stores, 4 no input shift; k_frames_seq: 8 no stores, 16 no loads, 32 no Salsa20, 64 no Poly1305, 128 stores to 64-byte-aligned places (whole lines); k_frames_lds: 512 no partial edge granules, 1024 the encode head as two aligned dwordx4
 #endif
 
 
@@ -57,17 +57,17 @@ __device__ __forceinline__ void seq_store4(uint64_t a, uint32_t x, uint32_t y, u
         *(G4_ *) (uintptr_t) a = (v4_){x, y, z, w};
 }
 
-#ifndef ZMQG_SEQ_LDSIN
-#define ZMQG_SEQ_LDSIN 1 // k_frames_seq: each window's input staged by the wave's LDS-DMA one window ahead (1; 0: per-lane loads)
-#endif
 #ifndef ZMQG_SEQ_COOPST
-#define ZMQG_SEQ_COOPST 2 // k_frames_seq decode under ZMQG_OPT_STREAM_OUT, 64-byte-aligned payloads: each step's chunks stored by the wave cooperatively (16 frames x 64 B per instruction) through LDS, a step later (2; 3: at the next step's top) or at once (1); 0: each lane its own always
+#define ZMQG_SEQ_COOPST 2 // k_frames_seq under ZMQG_OPT_STREAM_OUT (decode: 64-byte-aligned payloads): each step's chunks stored by the wave cooperatively (16 frames x 64 B per instruction) through LDS, a step later (2); 0: each lane its own always
 #endif
 #ifndef ZMQG_SEQ_SKIP5
 #define ZMQG_SEQ_SKIP5 1 // LDS-DMA input: no fifth granule for 16-byte-aligned frames (k_frames_seq, k_frames_lds)
 #endif
-#ifndef ZMQG_SEQ_PF
-#define ZMQG_SEQ_PF 1 // k_frames_seq: windows requested ahead of the one computed (1; 2 measured slower)
+#ifndef ZMQG_SEQ_LBREC
+#define ZMQG_SEQ_LBREC 1 // k_frames_seq decode, ordered grids of at most kFramesBS workgroups: the one-round look-back over self-validating records, each wave alone (0: lookback_excl, for timing)
+#endif
+#ifndef ZMQG_SEQ_UNI
+#define ZMQG_SEQ_UNI 1 // k_frames_seq: the specialised step for a wave whose 64 frames are all inside their streams (0: the general step always, for timing)
 #endif
 #ifndef ZMQG_SEQ_AL64
 #define ZMQG_SEQ_AL64 1 // k_frames_seq decode: 64-byte payload chunks when every payload of a wave starts 64-byte aligned (0: off, for timing)
@@ -79,6 +79,8 @@ __device__ __forceinline__ void seq_store4(uint64_t a, uint32_t x, uint32_t y, u
 
 #include "../../include/zmqg_curve.h"
 #include "curve_device.hpp"
+#include "curve_lbrec.hpp"
+#include <type_traits>
 
 namespace zmqg {
 
@@ -310,6 +312,7 @@ struct ReplayOut {
     unsigned long long *peer; // read (psnap); one session: written by the last workgroup
     unsigned long long *excl; // one session: per frame, for the body finisher
     unsigned long long *lb_flag, *lb_agg, *lb_inc; // one session: look-back state per ticket
+    unsigned long long *lb_rec; // one session, k_frames_seq: 2 x kFramesBS words, the one-round look-back's records (curve_lbrec.hpp)
     uint32_t ordered;         // 1: the whole grid is co-resident, so workgroups use blockIdx as
                               //    their look-back order (no ticket)
     uint32_t dbg;             // timing experiments only (tools/frames_bench): 1 no look-back, 2 no ticket
@@ -1063,50 +1066,6 @@ __global__ __launch_bounds__(kFramesBS) void k_frames(ZMQG_FRAMES_PARAMS)
     frames_g_impl<DEC, G, BigOp>(ZMQG_FRAMES_ARGS);
 }
 
-// Prefetch of words 1..16 of window w of a stream read in order (word 0 is
-// the previous window's word 16): dd[k] = the aligned word at A4 + 64w +
-// 4(k+1) (kept apart from word 0 so that they are an even register tuple),
-// four dwordx4, issued only where all 16 words are readable -- inside the
-// frame, or below the end of the wave's furthest frame (the caller's buffer
-// covers every frame, so reading up to that end stays inside it).  Returns
-// false where it issued nothing: that lane reloads its words exactly
-// (frame_load_exact) in the step that uses them.  The prefetch writes dd only
-// through these loads, so dd keeps the loads' register tuples from step to
-// step (a second writer of dd, e.g. a select, makes the compiler copy the
-// tuples and wait for the loads right where they are issued).
-__device__ __forceinline__ bool frame_prefetch(uint64_t A4, uint32_t lim, uint64_t wave_end, uint32_t w,
-                                               uint32_t dd[16])
-{
-    const uint64_t a = A4 + 64ull * w;
-    const bool ok = 64u * w + 68u <= lim || a + 68ull <= wave_end;
-    if (ok) {
-        // (ablation 256, timing only: the 64 bytes read from the 64-byte-aligned place below)
-        const GCU4a4 *p = (const GCU4a4 *) (uintptr_t) ((ZMQG_FRAMES_ABLATE & 256) ? (a & ~63ull) : a + 4ull);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const u32x4 tt = p[k];
-            dd[4 * k] = tt.x;
-            dd[4 * k + 1] = tt.y;
-            dd[4 * k + 2] = tt.z;
-            dd[4 * k + 3] = tt.w;
-        }
-    }
-    return ok;
-}
-
-// Words 1..16 of window w read one by one, a word past the stream's last one
-// from the last word's address instead (its bytes are >= S: masked or never
-// stored), so no word outside the stream is touched.
-__device__ __forceinline__ void frame_load_exact(uint64_t A4, uint32_t lim, uint32_t w, uint32_t dd[16])
-{
-    const uint32_t last = (lim - 1u) & ~3u; // offset of the last word holding a stream byte
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const uint32_t o = 64u * w + 4u * (k + 1);
-        dd[k] = *(GCU32 *) (uintptr_t) (A4 + (o <= last ? o : last));
-    }
-}
-
 // ---------------------------------------------------------------- one lane per frame
 // Wave-wide reductions and scans of the frame kernels' prologue on DPP
 // moves instead of LDS permutes (row_shr 1, 2, 4, 8 within rows of 16, then
@@ -1174,10 +1133,12 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 // register to the next window's store.  Measured against the G-lanes kernel
 // (k_frames) and its cost model in tools/frames_proto.hip, DESIGN.md
 // section 3:
-//   * The MAC of window w is absorbed in step w+1, unconditionally in the
-//     keystream's basic block, so the scheduler interleaves its multiply and
-//     carry chains with the Salsa20 rounds (at the batch sizes this kernel
-//     is chosen for, a wave is alone on its SIMD).
+//   * The MAC of window w is absorbed in step w+1, unconditionally, between
+//     the issue of the step's LDS reads and their first use: a wave alone on
+//     its SIMD issues the Salsa20 rounds every 4 cycles without it, and the
+//     MAC's ~150 independent instructions cover the reads' round trip.
+//   * A wave whose 64 frames are all inside their streams runs a step with
+//     its lane predicates constant and its DMA predicates as exec masks.
 //   * Each step issues the next window's loads and this window's stores
 //     together after the input has been consumed: the wait for them comes a
 //     whole Salsa20 block later (vmcnt counts loads and stores together, so
@@ -1230,6 +1191,11 @@ template <bool DEC, class BigOp, bool SO = false>
 __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
 {
     const bool lb = DEC && rp.lb_flag != nullptr;
+    // The one-round look-back (below): every workgroup's header-only
+    // aggregate as a self-validating record, read by each wave on its own at
+    // the end.  Not in a split launch, whose other body reads the flags.
+    const bool use_rec = ZMQG_SEQ_LBREC && lb && rp.ordered && rp.lb_rec != nullptr && gridDim.x <= kFramesBS &&
+                         ctl.split_wg == 0; // (kernel-uniform)
     // frames this body covers: all, or (k_frames_split) the first split_n
     const uint32_t nlim = ctl.split_wg ? ctl.split_n : n;
     SEQ_STAMP(0u);
@@ -1251,7 +1217,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     uint64_t A = 0, B = 0;
     int32_t status = 0;
     uint32_t hw[3] = {0, 0, 0};
-    uint32_t x0[16], d0 = 0; // window 0's stream words (decode: the wire; encode: payload bytes 0..), word 16
+    uint32_t x0[16]; // window 0's stream words (decode: the wire; encode: payload bytes 0..)
     auto fetch = [&](uint32_t wgv) {
         i = wgv * kFramesBS + threadIdx.x;
         valid = i < nlim;
@@ -1279,8 +1245,6 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             } else {
                 load_window(src, (int) L_in, x0);
             }
-            if (S > 64u)                                     // word 16: stream bytes 64-v.. (payload)
-                d0 = *(GCU32 *) (uintptr_t) ((A & ~3ull) + 64ull);
         } else {
             // the wire frame's first window: header, nonce, tag, 32 ciphertext bytes
             A = (uint64_t) (uintptr_t) src;
@@ -1289,7 +1253,6 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
 #pragma unroll
             for (int k = 0; k < 16; ++k)
                 x0[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], (uint32_t) A & 3u);
-            d0 = d[16];
             B = (uint64_t) (uintptr_t) dst - 33u;
         }
     };
@@ -1365,8 +1328,16 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             }
             if (lane > 0)
                 wexcl = up > wexcl ? up : wexcl;
-            if (threadIdx.x == 0)
-                lookback_publish(rp.lb_flag + wg, rp.lb_agg + wg, wagg, epoch, 1);
+            if (threadIdx.x == 0) {
+                if (use_rec) { // two relaxed stores, no wait between them or for the loads in flight
+                    __hip_atomic_store(rp.lb_rec + 2u * wg, lbrec_pack(epoch, (uint32_t) wagg), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(rp.lb_rec + 2u * wg + 1u, lbrec_pack(epoch, (uint32_t) (wagg >> 32)),
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    lookback_publish(rp.lb_flag + wg, rp.lb_agg + wg, wagg, epoch, 1);
+                }
+            }
         }
     }
     const bool is_big = valid && !small && S > 0;
@@ -1374,32 +1345,20 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         S = 0;
     const uint32_t nw = (S + 63u) >> 6;
     const uint32_t steps = __builtin_amdgcn_readfirstlane(wave_max_u32(nw));
-    const uint32_t v = (uint32_t) A & 3u;
-    const uint64_t A4 = A & ~3ull;
-    const uint32_t lim = S + v; // stream words whose first byte is below lim hold a stream byte
-    const uint64_t wave_end = wave_max_u64(nw ? A + S : 0); // end of the wave's furthest frame: reads below it stay in the buffer
-    // window 1's words (word 0 is window 0's word 16, d0); windows t and t+1
-    // alternate between the two buffers -- or, ZMQG_SEQ_PF 2, windows 1 and
-    // 2 are requested here and windows rotate over three buffers, each
-    // requested two steps before it is used (inputs from HBM rather than the
-    // Infinity Cache take longer than one keystream to arrive)
-    uint32_t ddA[16], ddB[16];
-    bool fastA = !ZMQG_SEQ_LDSIN && nw > 1u ? frame_prefetch(A4, lim, wave_end, 1u, ddA) : true, fastB = true;
-    // ZMQG_SEQ_LDSIN: the wave moves its 64 frames' window covers (five
-    // 16-byte granules each, the k_frames_lds input path) into one of two
-    // LDS buffers by LDS-DMA, a window ahead; pair j of lane l moves granule
-    // (64j + l) % 5 of frame (64j + l) / 5, so each instruction covers runs of
-    // whole 80-byte covers instead of 64 lanes' scattered 16-byte pieces, and
-    // the owning lane reads its window at its byte offset (unaligned
-    // ds_read_b128): no alignbyte shifts, no register buffers held across a
-    // keystream
-    __shared__ __attribute__((aligned(16))) uint8_t sq_lds[ZMQG_SEQ_LDSIN ? kFramesWaves * 2 * 64 * kStIn : 16];
-    uint8_t *const sq_w = sq_lds + (ZMQG_SEQ_LDSIN ? (threadIdx.x >> 6) * 2 * 64 * kStIn : 0u);
+    // The wave moves its 64 frames' window covers (five 16-byte granules
+    // each, the k_frames_lds input path) into one of two LDS buffers by
+    // LDS-DMA, a window ahead; pair j of lane l moves granule (64j + l) % 5 of
+    // frame (64j + l) / 5, so each instruction covers runs of whole 80-byte
+    // covers instead of 64 lanes' scattered 16-byte pieces, and the owning
+    // lane reads its window at its byte offset (unaligned ds_read_b128): no
+    // alignbyte shifts, no register buffers held across a keystream
+    __shared__ __attribute__((aligned(16))) uint8_t sq_lds[kFramesWaves * 2 * 64 * kStIn];
+    uint8_t *const sq_w = sq_lds + (threadIdx.x >> 6) * 2 * 64 * kStIn;
     const uint32_t sq_off = __builtin_amdgcn_readfirstlane((uint32_t) (uintptr_t) (StLdsVoid *) sq_w);
     const uint32_t sq_va = (uint32_t) A & 15u;
     uint64_t sq_la[5];
     uint32_t sq_rel[5], sq_lim[5];
-    if (ZMQG_SEQ_LDSIN) {
+    {
         const uint64_t Ab = A - sq_va;
         const uint32_t lm = S ? sq_va + S : 0u;
 #pragma unroll
@@ -1417,20 +1376,61 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         }
     }
     auto sq_dma = [&](uint32_t t) { // window t's covers -> buffer t & 1 (granules holding a stream byte)
-        const uint32_t b = sq_off + (t & 1u) * 64u * kStIn;
+        const uint32_t b = __builtin_amdgcn_readfirstlane(sq_off + (t & 1u) * 64u * kStIn);
 #pragma unroll
         for (uint32_t j = 0; j < 5; ++j)
             if (64u * t + sq_rel[j] < sq_lim[j])
                 lds_dma16(sq_la[j] + 64ull * t, b + 1024u * j);
     };
-    if (ZMQG_SEQ_LDSIN && steps > 1u)
+    // Uniform steps.  While window t + 1 lies wholly inside every one of the
+    // wave's 64 streams (t + 2 < the wave's smallest window count; a lane
+    // without a frame has none), each lane is active, off its tail and its
+    // last window, its previous window was four full blocks, and a granule of
+    // window t + 1 is moved exactly where it is moved at all (sq_lim != 0).
+    // Such a step takes its lane predicates as constants and its five DMA
+    // predicates as exec masks made once, here.
+    const uint32_t min_nw = __builtin_amdgcn_readfirstlane(~wave_max_u32(~nw));
+    uint64_t sq_m[5];
+#pragma unroll
+    for (uint32_t j = 0; j < 5; ++j)
+        sq_m[j] = __builtin_amdgcn_ballot_w64(sq_lim[j] != 0u);
+    auto sq_dma_uni = [&](uint32_t t) { // sq_dma(t) of a uniform step: one M0 and exec save, five masked moves
+        const uint32_t b = __builtin_amdgcn_readfirstlane(sq_off + (t & 1u) * 64u * kStIn);
+        uint64_t a[5];
+#pragma unroll
+        for (uint32_t j = 0; j < 5; ++j)
+            a[j] = sq_la[j] + 64ull * t;
+        unsigned keep;
+        uint64_t ex;
+        // (M0 and exec are the compiler's: saved and restored in the same
+        // statement; the exec write between an M0 write and the move that
+        // reads it is the wait state lds_dma16 spends on an s_nop)
+        asm volatile("s_mov_b32 %0, m0\n\t"
+                     "s_mov_b64 %1, exec\n\t"
+                     "s_mov_b32 m0, %7\n\t"
+                     "s_mov_b64 exec, %8\n\t"
+                     "global_load_lds_dwordx4 %2, off\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\t"
+                     "s_mov_b64 exec, %9\n\t"
+                     "global_load_lds_dwordx4 %3, off\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\t"
+                     "s_mov_b64 exec, %10\n\t"
+                     "global_load_lds_dwordx4 %4, off\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\t"
+                     "s_mov_b64 exec, %11\n\t"
+                     "global_load_lds_dwordx4 %5, off\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\t"
+                     "s_mov_b64 exec, %12\n\t"
+                     "global_load_lds_dwordx4 %6, off\n\t"
+                     "s_mov_b64 exec, %1\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(keep), "=&s"(ex)
+                     : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "s"(b), "s"(sq_m[0]), "s"(sq_m[1]),
+                       "s"(sq_m[2]), "s"(sq_m[3]), "s"(sq_m[4])
+                     : "memory", "scc");
+    };
+    if (steps > 1u && !(ZMQG_FRAMES_ABLATE & 16))
         sq_dma(1u);
-#if ZMQG_SEQ_PF == 2
-    uint32_t ddC[16];
-    bool fastC = true;
-    if (nw > 2u)
-        fastB = frame_prefetch(A4, lim, wave_end, 2u, ddB);
-#endif
 
     // Decode output in 64-byte payload chunks when every lane's payload
     // starts on a 64-byte boundary (wave-uniform; e.g. packed 1 KiB
@@ -1449,11 +1449,10 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     // the L2 wrote back as partial segments (WRITE_SIZE 1.41x the payload,
     // TCC_EA0_WRREQ_64B 1.49 M requests per launch for 1.05 M segments;
     // profiles/pmc_traffic_config2.json)
-    // ZMQG_SEQ_COOPST 2: a step's chunks go into the staging area at its end
-    // and leave in the next step -- read back at its top, stored after its
-    // keystream -- so the single wave on the SIMD never waits on the LDS
-    // round trip (form 1, read back and stored at once, costs the resident
-    // decode ~8 us per launch)
+    // A step's chunks go into the staging area at its end and leave in the
+    // next step -- read back at its top, stored after its keystream -- so
+    // the single wave on the SIMD never waits on the LDS round trip (read
+    // back and stored at once, they cost the resident decode ~8 us per launch)
     bool cs_pend = false; // the staging area holds the previous step's chunks
     // Layout granule-major (granule k of lane l's chunk at kStgPlane k + 16 l,
     // each plane padded by 16 bytes): a lane's four writes are four
@@ -1468,9 +1467,9 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     uint64_t cs_dst[4];
     uint32_t cs_nw[4];
     // (SO: the ZMQG_OPT_STREAM_OUT instantiation; al64 is wave-uniform)
-    // (encode, form 2 only: each window's 64 bytes at frame_store's 4-byte-
-    // aligned place, B - up + 64 t; the frame's last window stays per lane)
-    const bool coop = ZMQG_SEQ_COOPST && SO && (DEC ? al64 : ZMQG_SEQ_COOPST == 2);
+    // (encode: each window's 64 bytes at frame_store's 4-byte-aligned place,
+    // B - up + 64 t; the frame's last window stays per lane)
+    const bool coop = ZMQG_SEQ_COOPST && SO && (DEC ? al64 : true);
     if (coop) {
         const uint64_t cbase = DEC ? (uint64_t) (uintptr_t) dst : B - (((uint32_t) B & 3u) ? ((uint32_t) B & 3u) : 4u);
 #pragma unroll
@@ -1577,34 +1576,23 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     SEQ_STAMP(2u);
     call_state_count(zs);
 
-    // ---- steps 1 ..: window t (words in dd, prefetched by the previous
-    // step; the two buffers alternate so that the loads keep their register
-    // tuples)
-    auto step = [&](uint32_t t, uint32_t (&dd)[16], bool &fast, uint32_t (&dn)[16], bool &fastn) {
+    // ---- steps 1 ..: window t (its covers moved into LDS buffer t & 1 by
+    // the previous step).  UNI: a uniform step (above), the same body with
+    // the lane predicates constant.
+    auto step = [&](auto uni, uint32_t t) {
+        constexpr bool UNI = decltype(uni)::value;
         SEQ_STAMP(3u + t);
-        const bool act = t < nw;
-        // (COOPST 2) the previous step's staged chunks, read now, stored
-        // after the keystream
-        const bool had = ZMQG_SEQ_COOPST >= 2 && coop && cs_pend;
+        const bool act = UNI || t < nw;
+        // the previous step's staged chunks, read now, stored after the
+        // keystream
+        const bool had = ZMQG_SEQ_COOPST && coop && cs_pend;
         u32x4 cg[4];
         if (had) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 #pragma unroll
             for (uint32_t j = 0; j < 4; ++j)
                 cg[j] = *(const u32x4 *) stg_get(j);
-            if (ZMQG_SEQ_COOPST == 3) { // stored here, a whole keystream ahead of the next step's wait
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    if (t - 1u < cs_nw[j])
-                        seq_store4(cs_dst[j] + 64ull * (t - 2u), cg[j].x, cg[j].y, cg[j].z, cg[j].w);
-                cs_pend = false;
-            }
         }
-#if ZMQG_SEQ_PF == 2
-        // window t+2 into the buffer window t-1 has left
-        if (t + 2u < nw)
-            fastn = frame_prefetch(A4, lim, wave_end, t + 2u, dn);
-#endif
         uint32_t ks[16];
         if (ZMQG_FRAMES_ABLATE & 32) {
 #pragma unroll
@@ -1613,13 +1601,43 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         } else {
             salsa20_block(ks, key, n0, n1, t, 0);
         }
+        // (the keystream is pinned here, ahead of the wait: left to itself
+        // the compiler sinks it below the wait for this window's words)
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            asm volatile("" : "+v"(ks[k]));
+        SEQ_STAMP(24u + t);
+        // Window t's covers have landed (and the stores of a step ago are
+        // out of the way): the lane's four unaligned LDS reads go out, and
+        // the previous window's MAC -- ~150 VALU instructions that need only
+        // cp, pk and h -- issues while they are in flight; the XOR below is
+        // their first use.  h passes through a pin behind the reads, which
+        // as memory operations stay between the two statements, so the MAC
+        // cannot be scheduled ahead of them; h and the keystream pass
+        // through the pin after the MAC, so no XOR (and with it the wait for
+        // the reads) is scheduled into it.  (The words read are not pinned:
+        // a pin's register copy would wait for them.)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        uint32_t x[16];
+        {
+            const uint8_t *const p = sq_w + (t & 1u) * 64u * kStIn + kStIn * lane + sq_va;
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {
+                const u32x4 u = *(const u32x4_u1 *) (p + 16u * q);
+                x[4 * q] = u.x;
+                x[4 * q + 1] = u.y;
+                x[4 * q + 2] = u.z;
+                x[4 * q + 3] = u.w;
+            }
+        }
+        asm volatile("" : "+v"(h.h0), "+v"(h.h1), "+v"(h.h2), "+v"(h.h3), "+v"(h.h4));
         // The previous window's MAC (its ciphertext is in cp).  The
-        // four-block form runs for every lane, unconditionally, so that it
-        // shares a basic block with the keystream and the scheduler
-        // interleaves the two; lanes whose window was not four full blocks
-        // keep h and take the general form below.
-        const bool pv = t - 1u < nw;
-        const bool full = pv && cp_j0 == 0u && cp_len == 64u;
+        // four-block form runs for every lane, unconditionally, in the LDS
+        // reads' shadow; lanes whose window was not four full blocks keep h
+        // and take the general form below.
+        const bool pv = UNI || t - 1u < nw;
+        const bool full = UNI || (pv && cp_j0 == 0u && cp_len == 64u);
         {
             Poly32 hf = h;
             if (ZMQG_FRAMES_ABLATE & 64)
@@ -1632,62 +1650,18 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             h.h3 = full ? hf.h3 : h.h3;
             h.h4 = full ? hf.h4 : h.h4;
         }
-        // (keystream and MAC are pinned here, ahead of the next branch:
-        // left to itself the compiler sinks them into later blocks -- the
-        // keystream below the wait for this window's words)
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            asm volatile("" : "+v"(ks[k]));
-        asm volatile("" : "+v"(h.h0), "+v"(h.h1), "+v"(h.h2), "+v"(h.h3), "+v"(h.h4));
-        if (!(ZMQG_FRAMES_ABLATE & 64) && __builtin_amdgcn_ballot_w64(pv && !full) != 0) {
+        asm volatile(""
+                     : "+v"(h.h0), "+v"(h.h1), "+v"(h.h2), "+v"(h.h3), "+v"(h.h4), "+v"(ks[0]), "+v"(ks[1]), "+v"(ks[2]),
+                       "+v"(ks[3]), "+v"(ks[4]), "+v"(ks[5]), "+v"(ks[6]), "+v"(ks[7]), "+v"(ks[8]), "+v"(ks[9]),
+                       "+v"(ks[10]), "+v"(ks[11]), "+v"(ks[12]), "+v"(ks[13]), "+v"(ks[14]), "+v"(ks[15]));
+        if (!UNI && !(ZMQG_FRAMES_ABLATE & 64) && __builtin_amdgcn_ballot_w64(pv && !full) != 0) {
             if (pv && !full)
                 poly32_window(h, pk, cp, cp_j0, cp_len);
         }
-        SEQ_STAMP(24u + t);
-        uint32_t x[16], w16; // w16: this window's word 16 = the next window's word 0
-        if (ZMQG_SEQ_LDSIN) {
-            // window t's covers have landed (and the stores of a step ago
-            // are out of the way)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            const uint8_t *const p = sq_w + (t & 1u) * 64u * kStIn + kStIn * lane + sq_va;
-#pragma unroll
-            for (uint32_t q = 0; q < 4; ++q) {
-                const u32x4 u = *(const u32x4_u1 *) (p + 16u * q);
-                x[4 * q] = u.x;
-                x[4 * q + 1] = u.y;
-                x[4 * q + 2] = u.z;
-                x[4 * q + 3] = u.w;
-            }
-            w16 = 0;
-        } else if (__builtin_amdgcn_ballot_w64(act && !fast) != 0) {
-            // a lane whose words were not prefetched (the end of the wave's
-            // furthest frame) reads them exactly
-            uint32_t ee[16];
-            if (act && !fast)
-                frame_load_exact(A4, lim, t, ee);
-            const bool ex = act && !fast;
-            uint32_t e0 = ex ? ee[0] : dd[0];
-            x[0] = __builtin_amdgcn_alignbyte(e0, d0, v);
-#pragma unroll
-            for (int k = 1; k < 16; ++k) {
-                const uint32_t ek = ex ? ee[k] : dd[k];
-                x[k] = __builtin_amdgcn_alignbyte(ek, e0, v);
-                e0 = ek;
-            }
-            w16 = e0;
-        } else {
-            x[0] = __builtin_amdgcn_alignbyte(dd[0], d0, v);
-#pragma unroll
-            for (int k = 1; k < 16; ++k)
-                x[k] = __builtin_amdgcn_alignbyte(dd[k], dd[k - 1], v);
-            w16 = dd[15];
-        }
-        d0 = w16;
         if (t < 8u)
             SEQ_STAMP(44u + t);
-        const bool tail = act && S < 64u * t + 64u;
-        if (DEC && __builtin_amdgcn_ballot_w64(tail) != 0) {
+        const bool tail = !UNI && act && S < 64u * t + 64u;
+        if (!UNI && DEC && __builtin_amdgcn_ballot_w64(tail) != 0) {
             if (tail)
                 mask_tail(x, (int) (S - 64u * t));
         }
@@ -1695,7 +1669,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
 #pragma unroll
         for (int k = 0; k < 16; ++k)
             y[k] = x[k] ^ ks[k];
-        if (!DEC && __builtin_amdgcn_ballot_w64(tail) != 0) {
+        if (!UNI && !DEC && __builtin_amdgcn_ballot_w64(tail) != 0) {
             if (tail)
                 mask_tail(y, (int) (S - 64u * t));
         }
@@ -1703,23 +1677,20 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         for (int k = 0; k < 16; ++k)
             cp[k] = DEC ? x[k] : y[k];
         cp_j0 = 0;
-        cp_len = act ? (S - 64u * t < 64u ? S - 64u * t : 64u) : 0u;
-        // window t+1's loads and window t's stores, issued together after
-        // the input has been consumed: the wait for the loads comes a whole
+        cp_len = UNI ? 64u : act ? (S - 64u * t < 64u ? S - 64u * t : 64u) : 0u;
+        // window t+1's covers and window t's stores, issued together after
+        // the input has been consumed: the wait for the covers comes a whole
         // keystream later
-        if (ZMQG_FRAMES_ABLATE & 16) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                dn[k] = y[k] + k;
-            fastn = true;
-        } else if (ZMQG_SEQ_LDSIN) {
-            if (t + 1u < steps)
+        if (!(ZMQG_FRAMES_ABLATE & 16)) {
+            if (UNI)
+                sq_dma_uni(t + 1u);
+            else if (t + 1u < steps)
                 sq_dma(t + 1u);
-        } else if (ZMQG_SEQ_PF == 1 && t + 1u < nw) {
-            fastn = frame_prefetch(A4, lim, wave_end, t + 1u, dn);
         }
         if (t < 8u)
             SEQ_STAMP(52u + t);
+        const bool lastw = !UNI && act && t + 1u == nw;
+        const bool no_last = UNI || __builtin_amdgcn_ballot_w64(lastw) == 0; // no lane on its last window
         if (ZMQG_FRAMES_ABLATE & 8) {
             if (act && y[3] == 0x12345678u && y[7] == ycarry)
                 *(GU32 *) (uintptr_t) B = y[0];
@@ -1735,39 +1706,23 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             for (int k = 8; k < 16; ++k)
                 o[k] = __builtin_amdgcn_alignbyte(y[k - 7], y[k - 8], 1);
             uint8_t *const cdst = dst + 64u * (t - 1u);
-            const bool lastw = act && t + 1u == nw;
-            if (ZMQG_SEQ_COOPST == 2 && had) { // chunk t-2 of every frame that was active a step ago
+            if (had) { // chunk t-2 of every frame that was active a step ago
 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j)
-                    if (t - 1u < cs_nw[j])
+                    if (UNI || t - 1u < cs_nw[j])
                         seq_store4(cs_dst[j] + 64ull * (t - 2u), cg[j].x, cg[j].y, cg[j].z, cg[j].w);
                 cs_pend = false;
             }
-            if (ZMQG_SEQ_COOPST >= 2 && coop && __builtin_amdgcn_ballot_w64(lastw) == 0) {
-                // (no lane on its last window: every active frame's chunk is
-                // whole; a later step is certain -- the wave's longest frame
-                // has not reached its last window -- and stores them)
+            if (ZMQG_SEQ_COOPST && coop && no_last) {
+                // (every active frame's chunk is whole; a later step is
+                // certain -- the wave's longest frame has not reached its
+                // last window -- and stores them)
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // (after this step's reads)
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     *(u32x4 *) stg_put(k) = (u32x4){o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]};
                 cs_pend = true;
-            } else if (ZMQG_SEQ_COOPST == 1 && coop && __builtin_amdgcn_ballot_w64(lastw) == 0) {
-                // (no lane on its last window: every active frame's chunk is whole)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    *(u32x4 *) stg_put(k) = (u32x4){o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]};
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                u32x4 g[4];
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    g[j] = *(const u32x4 *) stg_get(j);
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    if (t < cs_nw[j])
-                        seq_store4(cs_dst[j] + 64ull * (t - 1u), g[j].x, g[j].y, g[j].z, g[j].w);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // (the reads before the next step's writes)
-            } else if (__builtin_amdgcn_ballot_w64(lastw) == 0) {
+            } else if (no_last) {
                 if (act) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -1798,19 +1753,18 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             for (int k = 0; k < 16; ++k)
                 yp[k] = y[k];
         } else {
-            const bool lastw = act && t + 1u == nw;
             if constexpr (!DEC) {
-                if (ZMQG_SEQ_COOPST == 2 && had) { // window t-1 of every frame that was active a step ago
+                if (had) { // window t-1 of every frame that was active a step ago
 #pragma unroll
                     for (uint32_t j = 0; j < 4; ++j)
-                        if (t - 1u < cs_nw[j])
+                        if (UNI || t - 1u < cs_nw[j])
                             seq_store4(cs_dst[j] + 64ull * (t - 1u), cg[j].x, cg[j].y, cg[j].z, cg[j].w);
                     cs_pend = false;
                 }
             }
-            if (!DEC && ZMQG_SEQ_COOPST == 2 && coop && __builtin_amdgcn_ballot_w64(lastw) == 0) {
-                // (no lane on its last window: each active frame's window is
-                // frame_store's whole 64 bytes; a later step stores them)
+            if (!DEC && ZMQG_SEQ_COOPST && coop && no_last) {
+                // (each active frame's window is frame_store's whole 64
+                // bytes; a later step stores them)
                 const uint32_t u = (uint32_t) B & 3u, sh = u ? 4u - u : 0u;
                 uint32_t o[16];
                 o[0] = __builtin_amdgcn_alignbyte(y[0], ycarry, sh);
@@ -1822,6 +1776,8 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
                 for (int k = 0; k < 4; ++k)
                     *(u32x4 *) stg_put(k) = (u32x4){o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]};
                 cs_pend = true;
+            } else if (UNI) {
+                frame_store(B, t, 0xffffffffu, y, ycarry, false); // (a whole window below the stream's end)
             } else if (act) {
                 frame_store(B, t, S, y, ycarry, lastw);
             }
@@ -1830,43 +1786,72 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         if (t < 8u)
             SEQ_STAMP(36u + t);
     };
-    // (both exits leave the loop: a skipped second step reaching the back
-    // edge would leave buffer B's loads outstanding at the loop head as far
-    // as the compiler's wait analysis knows, and every step would then wait
-    // for all loads before its first write of a buffer register)
     if (steps > 1u) {
-#if ZMQG_SEQ_PF == 2
 #pragma unroll 1
-        for (uint32_t t = 1;; t += 3) {
-            step(t, ddA, fastA, ddC, fastC);
-            if (t + 1u >= steps)
-                break;
-            step(t + 1u, ddB, fastB, ddA, fastA);
-            if (t + 2u >= steps)
-                break;
-            step(t + 2u, ddC, fastC, ddB, fastB);
-            if (t + 3u >= steps)
-                break;
+        for (uint32_t t = 1; t < steps; ++t) {
+            if (ZMQG_SEQ_UNI && t >= 2u && t + 2u < min_nw)
+                step(std::true_type{}, t);
+            else
+                step(std::false_type{}, t);
         }
-#else
-#pragma unroll 1
-        for (uint32_t t = 1;; t += 2) {
-            step(t, ddA, fastA, ddB, fastB);
-            if (t + 1u >= steps)
-                break;
-            step(t + 1u, ddB, fastB, ddA, fastA);
-            if (t + 2u >= steps)
-                break;
-        }
-#endif
     }
     SEQ_STAMP(60u);
+    // One-round look-back, each wave alone: lane l reads the records of the
+    // workgroups 1 + l, 65 + l, 129 + l and 193 + l below this one (a grid of
+    // at most kFramesBS workgroups: all of them).  The loads go out here,
+    // behind the last step's stores, and are used after the last window's MAC
+    // and the tag -- h passes through the statement behind them, so neither
+    // is scheduled ahead of the loads, and no wait lies in between.  (A lane
+    // with no such workgroup reads record 0 and drops it.)
+    unsigned long long rl[4] = {0, 0, 0, 0}, rh[4] = {0, 0, 0, 0};
+    if (use_rec) {
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+            const int k = (int) wg - 1 - (int) (lane + 64u * q);
+            const unsigned long long *const r = rp.lb_rec + 2u * (uint32_t) (k >= 0 ? k : 0);
+            rl[q] = __hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            rh[q] = __hip_atomic_load(r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("" : "+v"(h.h0), "+v"(h.h1), "+v"(h.h2), "+v"(h.h3), "+v"(h.h4)::"memory");
+    }
     // the last window's MAC
     if (steps > 0 && nw == steps)
         poly32_window(h, pk, cp, cp_j0, cp_len);
+    uint32_t tag[4]; // (of a lane without a stream: unused)
+    poly32_finish(h, spad, tag);
 
     unsigned long long excl = 0;
-    if (lb) {
+    if (use_rec) {
+        // a word whose valid bit and epoch tag are not this call's has not
+        // been written yet: only those are read again
+        unsigned long long P = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+            const int k = (int) wg - 1 - (int) (lane + 64u * q);
+            if (k >= 0) {
+                const unsigned long long *const r = rp.lb_rec + 2u * (uint32_t) k;
+                while (!lbrec_valid(rl[q], epoch)) {
+                    __builtin_amdgcn_s_sleep(1);
+                    rl[q] = __hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                while (!lbrec_valid(rh[q], epoch)) {
+                    __builtin_amdgcn_s_sleep(1);
+                    rh[q] = __hip_atomic_load(r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                P = max_u64(P, lbrec_value(rl[q], rh[q]));
+            }
+        }
+        P = wave_max_u64(P);
+        if (threadIdx.x == 0 && wg + 1 == gridDim.x) {
+            const unsigned long long inc = P > wagg ? P : wagg;
+            *rp.peer = inc > psn ? inc : psn;
+            if (rp.smax)
+                *rp.smax = inc;
+        }
+        excl = P > wexcl ? P : wexcl;
+        if (excl < psn)
+            excl = psn;
+    } else if (lb) {
         const unsigned long long P = lookback_excl(wg, epoch, rp.lb_flag, rp.lb_agg, rp.lb_inc);
         if (threadIdx.x == 0) {
             const unsigned long long inc = P > wagg ? P : wagg;
@@ -1912,8 +1897,6 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             fail_unprocessed(status, L_in, dst, flags_out + i, status_out + i, zs, ctl);
         return;
     }
-    uint32_t tag[4];
-    poly32_finish(h, spad, tag);
     if (!DEC) {
         if (S >= 64u) {
             // wire bytes 0..63: "\x07MESSAGE", nonce, tag, the first 32

@@ -150,6 +150,7 @@ struct Workspace {
     unsigned long long *lb_flag = nullptr;  // [cap] look-back state per workgroup ticket
     unsigned long long *lb_agg = nullptr;   // [cap]
     unsigned long long *lb_inc = nullptr;   // [cap]
+    unsigned long long *lb_rec = nullptr;   // [2 kFramesBS] k_frames_seq's one-round look-back records
     void *temp = nullptr;
     size_t temp_bytes = 0;
     unsigned long long *rt = nullptr; // replay tables: [tiles][S] then [row blocks][S] (also the nonce tables)
@@ -2054,9 +2055,10 @@ int ensure_workspace(zmqg_ctx *ctx, uint64_t n, hipStream_t st)
             (rc = grow(ctx, w.list_frame, cap, st)) || (rc = grow(ctx, w.post, cap, st)) ||
             (rc = grow(ctx, w.psnap, cap, st)) || (rc = grow(ctx, w.blockmax, cap, st)) ||
             (rc = grow(ctx, w.lb_flag, cap, st)) || (rc = grow(ctx, w.lb_agg, cap, st)) || (rc = grow(ctx, w.lb_inc, cap, st)) ||
-            (rc = grow(ctx, w.nonce, cap, st)))
+            (rc = grow(ctx, w.lb_rec, 2 * kFramesBS, st)) || (rc = grow(ctx, w.nonce, cap, st)))
             return rc;
         ZCHECK(ctx, hipMemsetAsync(w.lb_flag, 0, cap * sizeof(unsigned long long), st));
+        ZCHECK(ctx, hipMemsetAsync(w.lb_rec, 0, 2 * kFramesBS * sizeof(unsigned long long), st)); // (no record valid)
         if (!w.zs) {
             if ((rc = grow(ctx, w.zs, 1, st)))
                 return rc;
@@ -2477,7 +2479,7 @@ int zmqg_ctx_destroy(zmqg_ctx *ctx)
     Workspace &w = ctx->ws;
     void *ptrs[] = {w.hot, w.pw, w.fin, w.powtab, w.acc, w.cnt, w.nch, w.chunk_end, w.v, w.excl, w.v_s,
                     w.excl_s, w.iota, w.perm, w.keys_s, w.last, w.list_frame, w.post, w.psnap, w.blockmax, w.zs,
-                    w.lb_flag, w.lb_agg, w.lb_inc, w.temp, w.rt, w.nonce, w.stage, ctx->sessions, ctx->peer, ctx->send, ctx->zero_peer, ctx->dbuf};
+                    w.lb_flag, w.lb_agg, w.lb_inc, w.lb_rec, w.temp, w.rt, w.nonce, w.stage, ctx->sessions, ctx->peer, ctx->send, ctx->zero_peer, ctx->dbuf};
     for (void *p : ptrs)
         if (p)
             (void) hipFree(p);
@@ -2977,6 +2979,7 @@ static int decode_batch_impl(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, con
         rp.lb_flag = w.lb_flag;
         rp.lb_agg = w.lb_agg;
         rp.lb_inc = w.lb_inc;
+        rp.lb_rec = w.lb_rec;
         rp.smax = smax;
         // A grid that fits the device at once can use blockIdx as the
         // look-back order (every workgroup becomes resident eventually,

@@ -3,11 +3,14 @@
 the PMC passes of tools/pmc_profiles.sh (gpurun_out/pmcv, gpurun_out/pmct):
 per-launch VALU/SALU/VMEM wave-instruction counts and HBM bytes of the
 config-2 frame kernels, FETCH_SIZE scaled by the calibration copy of the same
-access shape (tools/framecopy.hip, LANE, one window in flight)."""
+access shape (tools/framecopy.hip, LANE, one window in flight).  Without
+the traffic passes (no pmct folder there: tools/pmc_valu_bench.sh alone) only
+profiles/pmc_valu_config2.json is written."""
 import collections
 import csv
 import glob
 import json
+import os
 import re
 import sys
 
@@ -49,16 +52,18 @@ try:
     stall = json.load(open(f"{root}/pmcs/summary.json"))
 except FileNotFoundError:
     stall = {}
+have_traffic = os.path.isdir(f"{root}/pmct")
 fcal, wcal = per_kernel(f"{root}/pmct/cal/fetch"), per_kernel(f"{root}/pmct/cal/write")
 moved_kib = N * P / 1024
 # the frame kernels' reads: LDS-DMA of whole 16-byte granules in runs of a
 # frame's five (k_frames_seq's staged input, k_frames_lds) -- the
 # calibration copy's cooperative shape (4 lanes per frame window); writes:
 # each lane's own 64-byte pieces -- the lane shape
-cal_f, _ = pick(fcal, r"k_copy<true, 1>", "FETCH_SIZE")
-cal_w, _ = pick(wcal, r"k_copy<false, 1>", "WRITE_SIZE")
-cal_f_lane, _ = pick(fcal, r"k_copy<false, 1>", "FETCH_SIZE")
-scale = moved_kib / cal_f
+if have_traffic:
+    cal_f, _ = pick(fcal, r"k_copy<true, 1>", "FETCH_SIZE")
+    cal_w, _ = pick(wcal, r"k_copy<false, 1>", "WRITE_SIZE")
+    cal_f_lane, _ = pick(fcal, r"k_copy<false, 1>", "FETCH_SIZE")
+    scale = moved_kib / cal_f
 EA = ("TCC_EA0_RDREQ_sum", "TCC_EA0_RDREQ_32B_sum", "TCC_EA0_WRREQ_sum", "TCC_EA0_WRREQ_64B_sum")
 
 
@@ -90,8 +95,8 @@ def traffic(form, dec):
 out_t, out_v = {}, {}
 for dec in (True, False):
     tag = "decode" if dec else "encode"
-    t = traffic("resident", dec)
-    kshort = t["kernel"]
+    t = traffic("resident", dec) if have_traffic else {}
+    kshort = t["kernel"] if have_traffic else "k_frames_seq<%s>" % tag
     v = valu["k_frames<%s>" % tag]
     vv = {"kernel": kshort, "valu_wave_instr_per_launch": v["SQ_INSTS_VALU"], "salu_instr_per_launch": v["SQ_INSTS_SALU"],
           "vmem_instr_per_launch": v["SQ_INSTS_VMEM"], "waves": v["SQ_WAVES"],
@@ -110,6 +115,25 @@ for dec in (True, False):
     else:
         out_t["encode"] = t
         out_v["encode"] = vv
+valu_meta = {
+    "source_id": build["source_id"], "commit": build["commit"],
+    "workload": "config2: 65536 x 1024 B frames, one session, one lane per frame (1024 waves, 1 per SIMD)",
+    "source": "rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES "
+              "--kernel-trace of python bench.py --eager --steps 3 --warmup 1 (tools/pmc_valu_bench.sh)",
+    "units": "wave instructions per launch (one VALU wave instruction = 64 lane operations; a wave alone on its "
+             "SIMD issues one every 4 cycles)",
+    "salsa20_lane_ops_per_frame_floor": 17 * 940,
+    "simds": 1024, "lanes_per_simd_per_cycle": 16, "clock_ghz_spec": 2.4, "clock_ghz_measured": 2.09,
+    "clock_note": "s_memtime over s_memrealtime per workgroup of the frame kernel (tools/frames_bench.hip): "
+                  "2.05-2.12 GHz per XCD under this load",
+    "peak_note": "16 lanes per cycle per SIMD: one wave per SIMD issues a VALU instruction every 4 cycles, and the "
+                 "Salsa20 instruction mix issues at that rate at every occupancy (profiles/valu_rates_r02.md)"}
+out_v.update(valu_meta)
+json.dump(out_v, open("profiles/pmc_valu_config2.json", "w"), indent=1)
+if not have_traffic:
+    print(json.dumps({"valu": {k: out_v[k] for k in ("kernel", "valu_wave_instr_per_launch",
+                                                      "valu_lane_ops_per_frame")}}))
+    sys.exit(0)
 out_t["hbm_fed"] = {"decode": traffic("hbm", True), "encode": traffic("hbm", False),
                     "form": "tools/hbm_probe.py --forms bench --stream-out: 8 config-2 batches with their own buffers, "
                             "8 encodes back to back then their 8 decodes with ZMQG_OPT_STREAM_OUT (bench.py hbm_fed); "
@@ -130,20 +154,6 @@ out_t.update({
                         "moved.  FETCH_SIZE counts the L2's memory-side requests, Infinity-Cache hits included: "
                         "the resident form's reads mostly hit the MALL, the HBM-fed form's come from HBM."
                         % (cal_f, moved_kib, cal_f_lane, scale, cal_w / moved_kib)})
-out_v.update({
-    "source_id": build["source_id"], "commit": build["commit"],
-    "workload": out_t["workload"],
-    "source": "rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES "
-              "--kernel-trace of python bench.py --eager --steps 3 --warmup 1 (tools/pmc_valu_bench.sh)",
-    "units": "wave instructions per launch (one VALU wave instruction = 64 lane operations; a wave alone on its "
-             "SIMD issues one every 4 cycles)",
-    "salsa20_lane_ops_per_frame_floor": 17 * 940,
-    "simds": 1024, "lanes_per_simd_per_cycle": 16, "clock_ghz_spec": 2.4, "clock_ghz_measured": 2.09,
-    "clock_note": "s_memtime over s_memrealtime per workgroup of the frame kernel (tools/frames_bench.hip): "
-                  "2.05-2.12 GHz per XCD under this load",
-    "peak_note": "16 lanes per cycle per SIMD: one wave per SIMD issues a VALU instruction every 4 cycles, and the "
-                 "Salsa20 instruction mix issues at that rate at every occupancy (profiles/valu_rates_r02.md)"})
 json.dump(out_t, open("profiles/pmc_traffic_config2.json", "w"), indent=1)
-json.dump(out_v, open("profiles/pmc_valu_config2.json", "w"), indent=1)
 print(json.dumps({"traffic": {k: out_t[k] for k in ("kernel", "read_bytes_per_launch", "write_bytes_per_launch")},
                   "valu": {k: out_v[k] for k in ("kernel", "valu_wave_instr_per_launch", "valu_lane_ops_per_frame")}}))
