@@ -437,7 +437,42 @@ int zmqg_notify_quiesce(zmqg_ctx *ctx);
  * zmqg_decode_zmtp_async: the same, without synchronising: `result` must be
  * device-accessible (device memory, or pinned host memory from
  * zmqg_host_alloc) and holds the result once the stream reaches this point
- * (zmqg_fence_record / _query). */
+ * (zmqg_fence_record / _query).
+ *
+ * zmqg_decode_zmtp_multi: the same decoder (src/v2_decoder.cpp:35-140,
+ * maxmsgsize :74-84) over the receive buffers of many connections in one
+ * asynchronous call -- an I/O thread's shape: n_streams buffers of at most
+ * in_batch_size bytes each (src/options.cpp:221) -- with the semantics of
+ * n_streams zmqg_decode_zmtp calls in stream order.  Stream s is
+ * in[stream_off[s] .. +stream_len[s]), received on session stream_sid[s];
+ * streams do not overlap, any byte alignment of stream_off is valid,
+ * stream_len[s] < 2^31, and no byte outside a stream is read (nothing
+ * between two streams is parsed).  The three stream arrays, the per-frame
+ * arrays and results (n_streams entries) are device-accessible; the host
+ * reads nothing back.  Every per-frame array holds n_streams * max_frames
+ * entries (<= 2^31 - 1, else -EINVAL); stream s owns slots [s * max_frames,
+ * (s + 1) * max_frames): slot s * max_frames + j, j < results[s].frames,
+ * describes the stream's j-th frame as zmqg_decode_zmtp would -- frame_in_off
+ * = out_off = the body's absolute offset in `in` (`out` may be `in`; otherwise
+ * `out` spans the same offsets), frame_len the body size, flags_out the
+ * plaintext bits with the frame's MORE / COMMAND bits ORed in, status_out as
+ * for zmqg_decode_batch -- and the stream's remaining slots hold empty frames
+ * (offset 0, length 0, a malformed status, flags 0).  results[s]: frames,
+ * consumed (relative to stream_off[s]; an incomplete last frame is left for
+ * the next call), out_bytes (the stream's payload bytes), error (0, or
+ * EMSGSIZE where a size exceeds max_msg_size or 2^32 - 1: that stream ends
+ * there, the frames before it are returned).  A complete frame that is not a
+ * MESSAGE command is returned as its stream's last frame; a stream with more
+ * than max_frames frames returns the first max_frames.  No stream's outcome
+ * depends on another stream's bytes.  Replay and peer nonces are as if
+ * curve_encoding_t::decode ran on all returned frames in slot order (stream
+ * 0's frames, then stream 1's, ...): two streams may name one session, the
+ * later one then sees the earlier one's nonces; stream_sid[s] >= max_sessions
+ * gives that stream's frames ZMQG_ERR_SESSION.  With n_streams == 0 nothing is
+ * done; with max_frames == 0 results is zero-filled on the stream.  The call
+ * is one launch more than zmqg_decode_batch_ex (one workgroup per stream
+ * parses it in LDS); ZMQG_OPT_VERIFY_FIRST / _REPLAY_HOST / _STREAM_OUT are
+ * not offered on this call. */
 typedef struct zmqg_zmtp_result {
     uint64_t frames;
     uint64_t consumed;
@@ -456,6 +491,11 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
                            uint64_t max_frames, uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off,
                            uint8_t *out, uint8_t *flags_out, int32_t *status_out, zmqg_zmtp_result *result,
                            void *stream);
+int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid,
+                           const uint64_t *stream_off, const uint32_t *stream_len, const uint8_t *in,
+                           int64_t max_msg_size, uint64_t max_frames, uint64_t *frame_in_off, uint32_t *frame_len,
+                           uint64_t *out_off, uint8_t *out, uint8_t *flags_out, int32_t *status_out,
+                           zmqg_zmtp_result *results, void *stream);
 
 /* Handshake key derivation in batches, one
  * 32-byte item per thread, items packed back to back:

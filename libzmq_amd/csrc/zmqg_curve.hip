@@ -54,6 +54,7 @@
 #include "curve_z85.hpp"
 #include "curve_x25519.hpp"
 #include "curve_zmtp.hpp"
+#include "curve_zmtp_multi.hpp"
 
 #ifndef ZMQG_ABLATE
 #define ZMQG_ABLATE 0
@@ -3360,6 +3361,23 @@ static int zmtp_temp(zmqg_ctx *ctx, size_t need, hipStream_t st)
     return 0;
 }
 
+// the receive side's per-frame buffers for n frames (under ctx->mu)
+static int zmtp_frame_cap(zmqg_ctx *ctx, uint64_t n, hipStream_t st)
+{
+    ZmtpWs &z = ctx->zw;
+    if (n <= z.f_cap)
+        return 0;
+    uint64_t cap = z.f_cap ? z.f_cap : 1024;
+    while (cap < n)
+        cap *= 2;
+    int rc;
+    if ((rc = grow(ctx, z.run, 2 * (cap + 1), st)) || (rc = grow(ctx, z.runpre, cap + 1, st)) ||
+        (rc = grow(ctx, z.sid_fill, cap, st)) || (rc = grow(ctx, z.fflags, cap, st)))
+        return rc;
+    z.f_cap = cap;
+    return 0;
+}
+
 int zmqg_encode_zmtp(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, const uint64_t *nonce, const uint8_t *flags,
                      const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
                      uint64_t *frame_off, void *stream)
@@ -3439,15 +3457,8 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
             return rc;
         z.c_cap = cap;
     }
-    if (max_frames > z.f_cap) {
-        uint64_t cap = z.f_cap ? z.f_cap : 1024;
-        while (cap < max_frames)
-            cap *= 2;
-        if ((rc = grow(ctx, z.run, 2 * (cap + 1), st)) || (rc = grow(ctx, z.runpre, cap + 1, st)) ||
-            (rc = grow(ctx, z.sid_fill, cap, st)) || (rc = grow(ctx, z.fflags, cap, st)))
-            return rc;
-        z.f_cap = cap;
-    }
+    if ((rc = zmtp_frame_cap(ctx, max_frames, st)))
+        return rc;
     if (!z.walk && (rc = grow(ctx, z.walk, 1, st)))
         return rc;
     const uint32_t g = (uint32_t) nwg;
@@ -3504,6 +3515,50 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
     // result copied from the parse state, by the decode's frame kernel)
     return decode_batch_impl(ctx, max_frames, z.sid_fill, frame_in_off, frame_len, in, out_off, out, flags_out,
                              status_out, o.max_len ? &o : nullptr, z.fflags, z.walk, result, stream);
+}
+
+int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
+                           const uint32_t *stream_len, const uint8_t *in, int64_t max_msg_size, uint64_t max_frames,
+                           uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off, uint8_t *out,
+                           uint8_t *flags_out, int32_t *status_out, zmqg_zmtp_result *results, void *stream)
+{
+    if (!ctx || !results || check_n(n_streams) || check_n(max_frames) || check_n(n_streams * max_frames))
+        return -EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    if (n_streams == 0)
+        return 0;
+    if (max_frames == 0) {
+        ZCHECK(ctx, hipMemsetAsync(results, 0, n_streams * sizeof *results, st));
+        return 0;
+    }
+    if (!stream_sid || !stream_off || !stream_len || !in || !frame_in_off || !frame_len || !out_off || !out ||
+        !flags_out || !status_out)
+        return -EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ZmtpWs &z = ctx->zw;
+    const uint64_t slots = n_streams * max_frames;
+    int rc;
+    // (the per-frame arrays are the ctx's: after the work queued on its last stream)
+    if ((rc = order_after_last(ctx, st)) || (rc = zmtp_frame_cap(ctx, slots, st)))
+        return rc;
+    // one workgroup per stream, a persistent grid beyond what is resident
+    // (21 KiB of LDS a workgroup: 7 per CU)
+    const uint64_t resident = 7ull * (uint64_t) (ctx->cus > 0 ? ctx->cus : 256);
+    const uint32_t g = (uint32_t) (n_streams < resident ? n_streams : resident);
+    hipLaunchKernelGGL(k_zmtp_streams, dim3(g), dim3(kZmtpMultiThreads), 0, st, (uint32_t) n_streams, stream_sid,
+                       stream_off, stream_len, in, max_msg_size, max_frames, frame_in_off, frame_len, out_off,
+                       z.sid_fill, z.fflags, results);
+    ZCHECK(ctx, hipGetLastError());
+    // the decode over every slot (as zmqg_decode_zmtp_async: the empty frames
+    // fail as malformed; a maxmsgsize within the frame kernel's range skips
+    // the large-frame launches); the results are already in place
+    zmqg_batch_opts o{};
+    o.size = sizeof o;
+    if (max_msg_size >= 0 && (uint64_t) max_msg_size <= kMaxFrameStream)
+        o.max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
+    return decode_batch_impl(ctx, slots, z.sid_fill, frame_in_off, frame_len, in, out_off, out, flags_out, status_out,
+                             o.max_len ? &o : nullptr, z.fflags, nullptr, nullptr, stream);
 }
 
 int zmqg_decode_zmtp(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint64_t in_bytes, int64_t max_msg_size,

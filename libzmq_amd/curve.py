@@ -91,6 +91,8 @@ _lib.zmqg_encode_zmtp.argtypes = [_P, _U64] + [_P] * 9
 _lib.zmqg_decode_zmtp.argtypes = [_P, _U32, _P, _U64, ctypes.c_int64, _U64] + [_P] * 6 + [ctypes.POINTER(ZmtpResult),
                                                                                        _P]
 _lib.zmqg_decode_zmtp_async.argtypes = [_P, _U32, _P, _U64, ctypes.c_int64, _U64] + [_P] * 8
+_lib.zmqg_decode_zmtp_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int64, _U64] + [_P] * 8
+ZMTP_MULTI_TILE = 16384  # kZmtpMultiTile: bytes of a stream zmqg_decode_zmtp_multi's kernel holds in LDS at a time
 _lib.zmqg_scalarmult_batch.argtypes = [_P, _U64] + [_P] * 5
 _lib.zmqg_box_beforenm_batch.argtypes = [_P, _U64] + [_P] * 5
 _lib.zmqg_box_afternm_batch.argtypes = [_P, _U64] + [_P] * 8
@@ -330,6 +332,29 @@ class CurveContext:
         r = result.cpu().numpy().view(np.uint64)
         return dict(frames=int(r[0]), consumed=int(r[1]), out_bytes=int(r[2]),
                     error=int(np.int32(r[3] & np.uint64(0xffffffff))))
+
+    def decode_zmtp_multi(self, stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                          frame_len, out_off, out, flags_out, status_out, results, stream=None):
+        """Parse and decode the receive buffers of many connections in one
+        asynchronous call: stream s is inp[stream_off[s] .. +stream_len[s]) on
+        session stream_sid[s] (int32 / int64 / int32 tensors of n_streams
+        entries).  The per-frame tensors hold n_streams * max_frames entries,
+        stream s owning slots [s * max_frames, (s + 1) * max_frames); `results`
+        is a device int64 tensor of n_streams x 4 (one zmqg_zmtp_result per
+        stream), read with zmtp_results() once the stream is done."""
+        n = int(stream_sid.numel())
+        self._check(_lib.zmqg_decode_zmtp_multi(self._ctx, n, _ptr(stream_sid), _ptr(stream_off), _ptr(stream_len),
+                                                _ptr(inp), max_msg_size, max_frames, _ptr(frame_in_off),
+                                                _ptr(frame_len), _ptr(out_off), _ptr(out), _ptr(flags_out),
+                                                _ptr(status_out), _ptr(results), _stream_handle(stream)),
+                    "zmqg_decode_zmtp_multi")
+
+    @staticmethod
+    def zmtp_results(results):
+        """decode_zmtp_multi's `results` (synchronised) as a list of dicts, one per stream."""
+        r = results.cpu().numpy().view(np.uint64).reshape(-1, 4)
+        return [dict(frames=int(x[0]), consumed=int(x[1]), out_bytes=int(x[2]),
+                     error=int(np.int32(x[3] & np.uint64(0xffffffff)))) for x in r]
 
     # ---- handshake key derivation (device tensors of n x 32 bytes) ----
     def scalarmult_batch(self, scalar, point, out, status_out, stream=None):
