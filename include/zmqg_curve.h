@@ -497,6 +497,76 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
                            uint64_t *out_off, uint8_t *out, uint8_t *flags_out, int32_t *status_out,
                            zmqg_zmtp_result *results, void *stream);
 
+/* zmqg_encode_zmtp_multi: the send side of an I/O thread in one asynchronous
+ * call.  The n outgoing messages come in arrival (batch) order, interleaved
+ * over n_streams connections (A1 B1 A2 C1 B2 ...); every connection gets its
+ * own contiguous run of ZMTP frames in `out`, ready for send() -- what
+ * stream_engine_base_t::out_event builds per connection in _outpos
+ * (src/stream_engine_base.cpp:314-380: the pull loop :331, the ZMTP encoder
+ * :343, src/v2_encoder.cpp:23-60; out_batch_size, src/options.cpp:222).  The
+ * batch is not sorted and the host reads nothing back; all arrays are
+ * device-accessible.  Frame i belongs to stream frame_stream[i], which sends
+ * on session stream_sid[frame_stream[i]].
+ *
+ * Validity.  A stream is valid when stream_sid[s] < max_sessions; a frame is
+ * valid when frame_stream[i] < n_streams and its stream is valid.
+ * Sizes.  For a valid frame W = zmqg_wire_size(flags[i], the session's
+ * downgrade_sub, len[i]) and F(i) = W + (W > 255 ? 9 : 2), as in
+ * zmqg_encode_zmtp.
+ * Layout.  B(s) = the sum of F over the valid frames of stream s (0 for an
+ * invalid stream); base(s) = the sum of B(t), t < s: the regions are packed
+ * back to back in stream order; pos(i) = the sum of F(j) over the valid frames
+ * j < i of the same stream.  frame_off[i] = base(stream) + pos(i) for a valid
+ * frame, UINT64_MAX for an invalid one, and frame_off[n] = the sum of all B
+ * (n + 1 entries).
+ * Fit.  A valid frame fits when frame_off[i] + F(i) <= out_bytes (checked on
+ * the device, as ZMQG_OPT_VERIFY_FIRST's out_bytes is: `out` is typically a
+ * pinned slot of fixed size).  Offsets rise within a stream, so the fitting
+ * frames of a stream are a prefix of it.
+ *   - a valid frame that fits: its ZMTP header and MESSAGE command are written
+ *     at out[frame_off[i] .. +F(i)), the bytes zmqg_encode_zmtp would write for
+ *     that frame; status_out[i] = 0.
+ *   - a valid frame that does not fit: nothing of it is written, status_out[i]
+ *     = ZMQG_ERR_BOUND, frame_off[i] keeps its computed value, and it consumes
+ *     no nonce.
+ *   - an invalid frame: nothing is written, status_out[i] = ZMQG_ERR_SESSION.
+ * Nonces.  nonce != NULL: frame i uses nonce[i] (the caller resubmits a frame
+ * that did not fit with the same nonce).  nonce == NULL: the nonces come from
+ * the sessions' device send counters, as under ZMQG_OPT_NONCE_AUTO, taken in
+ * batch order over the fitting frames of each session; each counter advances
+ * by its number of fitting frames.  Two streams may name one session: a later
+ * frame in batch order then takes the later nonce, whichever stream it is in.
+ * max_sessions > 8192 with nonce == NULL gives -EINVAL.
+ * results[s] (n_streams entries): frames = the stream's fitting frames,
+ * out_off = base(s), out_bytes = the sum of their F -- out[out_off ..
+ * +out_bytes) goes to the socket, and on the peer these two are exactly
+ * zmqg_decode_zmtp_multi's stream_off / stream_len -- and error = EINVAL for
+ * an invalid stream (frames 0, bytes 0), ENOBUFS when a valid frame of the
+ * stream did not fit, else 0.
+ * No byte of `out` is written outside the ranges of fitting frames, and
+ * nothing at or past out_bytes.  `out` must not overlap `in`.  status_out may
+ * be NULL.  Frames of any size (those above 4.5 KiB go through the large-frame
+ * kernels as in zmqg_encode_batch).  ZMQG_OPT_STREAM_OUT and max_len are not
+ * offered on this call.
+ * Returns -EINVAL for a null ctx, n_streams > 8192, n_streams == 0 with n > 0,
+ * a null results or stream_sid with n_streams > 0, a null frame_off, a null
+ * required array with n > 0, n > 2^31 - 1; -ENOMEM / -EIO as elsewhere.  With
+ * n == 0, frame_off[0] = 0 and every results[s] is filled (frames 0, bytes 0,
+ * out_off 0, error 0 or EINVAL) on the stream.  Five launches before the
+ * encode's own (nine with device nonces), whatever n and n_streams are. */
+typedef struct zmqg_zmtp_send_result {
+    uint64_t frames;     /* frames of this stream that were encoded */
+    uint64_t out_off;    /* start of the stream's region in `out` */
+    uint64_t out_bytes;  /* bytes of the encoded frames: out[out_off .. +out_bytes) goes to the socket */
+    int32_t error;       /* 0, ENOBUFS, EINVAL */
+    int32_t pad;
+} zmqg_zmtp_send_result;
+int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                           const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                           const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
+                           uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                           zmqg_zmtp_send_result *results, void *stream);
+
 /* Handshake key derivation in batches, one
  * 32-byte item per thread, items packed back to back:
  *   zmqg_scalarmult_batch: crypto_scalarmult_curve25519(out, scalar, point)

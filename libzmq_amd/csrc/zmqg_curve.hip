@@ -55,6 +55,7 @@
 #include "curve_x25519.hpp"
 #include "curve_zmtp.hpp"
 #include "curve_zmtp_multi.hpp"
+#include "curve_zmtp_send.hpp"
 
 #ifndef ZMQG_ABLATE
 #define ZMQG_ABLATE 0
@@ -198,6 +199,11 @@ struct ZmtpWs {
     ZmtpResHost *res_dev = nullptr;       // (its device address)
     void *temp = nullptr;
     size_t temp_bytes = 0;
+    uint64_t s_cap = 0;                   // zmqg_encode_zmtp_multi: frames
+    uint32_t *s_sid = nullptr;            // [s_cap] the session each frame is encoded on (or none)
+    uint64_t *s_woff = nullptr;           // [s_cap] body offsets
+    unsigned long long *s_tab = nullptr;  // [tiles][streams], [row blocks][streams], bases and totals [2][streams]
+    size_t s_tab_cap = 0;
 };
 } // namespace
 
@@ -2299,12 +2305,13 @@ uint32_t replay_tile_frames(uint32_t nn, uint32_t S)
 
 // ZMQG_OPT_NONCE_AUTO over several sessions: each frame's nonce into w.nonce
 // (k_nonce_*), advancing the sessions' send counters, on `st` before the
-// frame kernel.
-int nonce_multi(zmqg_ctx *ctx, uint32_t nn, const uint32_t *sid, hipStream_t st)
+// frame kernel.  T: the frames per tile (a multiple of 64), 0 = replay_tile_frames.
+int nonce_multi(zmqg_ctx *ctx, uint32_t nn, const uint32_t *sid, hipStream_t st, uint32_t T = 0)
 {
     Workspace &w = ctx->ws;
     const uint32_t S = ctx->max_sessions;
-    const uint32_t T = replay_tile_frames(nn, S);
+    if (!T)
+        T = replay_tile_frames(nn, S);
     const uint32_t tiles = (nn + T - 1) / T, rbs = (tiles + kReplayRB - 1) / kReplayRB;
     const size_t need = ((size_t) tiles + rbs + 1) * S; // tables, block sums, send snapshot
     if (need > w.rt_cap) {
@@ -2487,7 +2494,8 @@ int zmqg_ctx_destroy(zmqg_ctx *ctx)
     {
         ZmtpWs &z = ctx->zw;
         void *zp[] = {z.F,      z.wire_off, z.cand_wg, z.count_wg, z.off_wg, z.cand, z.nb,   z.first_w,
-                      z.wid,    z.run,      z.runpre,  z.sid_fill, z.fflags, z.walk, z.temp, z.count16, z.cdesc, z.cflag};
+                      z.wid,    z.run,      z.runpre,  z.sid_fill, z.fflags, z.walk, z.temp, z.count16, z.cdesc, z.cflag,
+                      z.s_sid,  z.s_woff,   z.s_tab};
         for (void *p : zp)
             if (p)
                 (void) hipFree(p);
@@ -3415,6 +3423,108 @@ int zmqg_encode_zmtp(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, const uint6
     hipLaunchKernelGGL(k_zmtp_headers, dim3(g0), dim3(256), 0, st, n, frame_off, out, z.wire_off);
     ZCHECK(ctx, hipGetLastError());
     return zmqg_encode_batch(ctx, n, sid, nonce, flags, in_off, len, in, z.wire_off, out, stream);
+}
+
+// Frames per tile of zmqg_encode_zmtp_multi's tables (k_zsend_*, and k_nonce_*
+// there).  A tile is walked in order, at a cost per frame that does not depend
+// on the keys, so tiles stay small -- 256 frames, and a batch spreads over the
+// chip -- until the table (tiles x keys entries) passes 4 Mi entries or
+// kZsendMaxTiles rows.
+static uint32_t zsend_tile_frames(uint32_t nn, uint32_t keys)
+{
+    uint32_t T = 256;
+    for (;;) {
+        const uint64_t tiles = ((uint64_t) nn + T - 1) / T;
+        if (tiles <= kZsendMaxTiles && tiles * keys <= (4ull << 20))
+            return T;
+        T *= 2;
+    }
+}
+
+int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                           const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                           const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
+                           uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                           zmqg_zmtp_send_result *results, void *stream)
+{
+    if (!ctx || check_n(n) || n_streams > kZsendMaxStreams || (n_streams == 0 && n > 0) || !frame_off)
+        return -EINVAL;
+    if (n_streams > 0 && (!results || !stream_sid))
+        return -EINVAL;
+    if (!nonce && ctx->max_sessions > kReplayMaxSessions)
+        return -EINVAL;
+    if (n > 0 && (!frame_stream || !flags || !in_off || !len || !in || !out))
+        return -EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    if (n_streams == 0) {
+        ZCHECK(ctx, hipMemsetAsync(frame_off, 0, sizeof(uint64_t), st));
+        return 0;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ZmtpWs &z = ctx->zw;
+    const uint32_t nn = (uint32_t) n, NS = (uint32_t) n_streams;
+    const uint32_t T = zsend_tile_frames(nn, NS);
+    const uint32_t tiles = (nn + T - 1) / T, rbs = (tiles + kZsendRB - 1) / kZsendRB;
+    int rc;
+    // (the buffers are the ctx's: after the work queued on its last stream)
+    if ((rc = order_after_last(ctx, st)))
+        return rc;
+    if (n > z.s_cap) {
+        uint64_t cap = z.s_cap ? z.s_cap : 1024;
+        while (cap < n)
+            cap *= 2;
+        if ((rc = grow(ctx, z.s_sid, cap, st)) || (rc = grow(ctx, z.s_woff, cap, st)))
+            return rc;
+        z.s_cap = cap;
+    }
+    const size_t need = ((size_t) tiles + rbs + 2) * NS; // tables, block sums, bases, totals
+    if (need > z.s_tab_cap) {
+        size_t cap = z.s_tab_cap ? z.s_tab_cap : 4096;
+        while (cap < need)
+            cap *= 2;
+        z.s_tab_cap = 0;
+        if ((rc = grow(ctx, z.s_tab, cap, st)))
+            return rc;
+        z.s_tab_cap = cap;
+    }
+    unsigned long long *tab = z.s_tab, *blk = tab + (size_t) tiles * NS, *base = blk + (size_t) rbs * NS,
+                       *tot = base + NS;
+    const dim3 cg((NS + 255) / 256, rbs);
+    if (tiles) {
+        hipLaunchKernelGGL(k_zsend_tiles, dim3(tiles), dim3(256), NS * sizeof(unsigned long long), st, nn, T, NS,
+                           stream_sid, frame_stream, flags, len, (const DevSession *) ctx->sessions,
+                           ctx->max_sessions, tab, tot);
+        ZCHECK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_zsend_colblk, cg, dim3(256), 0, st, tiles, NS, (const unsigned long long *) tab, blk,
+                           tot);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_zsend_base, dim3(1), dim3(kZsendBaseThreads), 0, st, NS, stream_sid, ctx->max_sessions,
+                       (const unsigned long long *) (tiles ? tot : nullptr), out_bytes, base, results, frame_off + n);
+    ZCHECK(ctx, hipGetLastError());
+    if (!tiles)
+        return 0;
+    hipLaunchKernelGGL(k_zsend_colscan, cg, dim3(256), 0, st, tiles, NS, tab, (const unsigned long long *) blk,
+                       (const unsigned long long *) base);
+    ZCHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_zsend_frames, dim3(tiles), dim3(kZsendFramesThreads), NS * sizeof(unsigned long long), st, nn,
+                       T, NS, stream_sid, frame_stream, flags, len, (const DevSession *) ctx->sessions, ctx->max_sessions,
+                       (const unsigned long long *) tab, (const unsigned long long *) base, out_bytes, out, frame_off,
+                       status_out, z.s_sid, z.s_woff, results);
+    ZCHECK(ctx, hipGetLastError());
+    // The encode over all n frames: one that is invalid or does not fit has
+    // no session there, so it is neither written nor given a nonce.  Device
+    // nonces (get_and_inc_nonce in batch order, src/curve_mechanism_base.hpp:41)
+    // go through the session tables whatever max_sessions is: the frame
+    // kernel's own counter would count the frames that are left out.
+    if (!nonce) {
+        if ((rc = ensure_workspace(ctx, n, st)) ||
+            (rc = nonce_multi(ctx, nn, z.s_sid, st, zsend_tile_frames(nn, ctx->max_sessions))))
+            return rc;
+        nonce = ctx->ws.nonce;
+    }
+    return zmqg_encode_batch_ex(ctx, n, z.s_sid, nonce, flags, in_off, len, in, z.s_woff, out, nullptr, stream);
 }
 
 int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint64_t in_bytes, int64_t max_msg_size,

@@ -92,6 +92,7 @@ _lib.zmqg_decode_zmtp.argtypes = [_P, _U32, _P, _U64, ctypes.c_int64, _U64] + [_
                                                                                        _P]
 _lib.zmqg_decode_zmtp_async.argtypes = [_P, _U32, _P, _U64, ctypes.c_int64, _U64] + [_P] * 8
 _lib.zmqg_decode_zmtp_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int64, _U64] + [_P] * 8
+_lib.zmqg_encode_zmtp_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 7 + [_U64] + [_P] * 4
 ZMTP_MULTI_TILE = 16384  # kZmtpMultiTile: bytes of a stream zmqg_decode_zmtp_multi's kernel holds in LDS at a time
 _lib.zmqg_scalarmult_batch.argtypes = [_P, _U64] + [_P] * 5
 _lib.zmqg_box_beforenm_batch.argtypes = [_P, _U64] + [_P] * 5
@@ -354,6 +355,35 @@ class CurveContext:
         """decode_zmtp_multi's `results` (synchronised) as a list of dicts, one per stream."""
         r = results.cpu().numpy().view(np.uint64).reshape(-1, 4)
         return [dict(frames=int(x[0]), consumed=int(x[1]), out_bytes=int(x[2]),
+                     error=int(np.int32(x[3] & np.uint64(0xffffffff)))) for x in r]
+
+    def encode_zmtp_multi(self, stream_sid, frame_stream, nonce, flags, in_off, length, inp, out, frame_off,
+                          status_out, results, stream=None, out_bytes=None):
+        """Encode and frame n messages that arrive interleaved over many
+        connections, in one asynchronous call: frame i belongs to stream
+        frame_stream[i] (int32, n entries), which sends on session
+        stream_sid[frame_stream[i]] (int32, n_streams entries); every stream's
+        frames land in a contiguous region of `out`, the regions packed in
+        stream order.  nonce None: the sessions' device send counters.
+        out_bytes: the capacity of `out` (default: the tensor's extent); a
+        frame that would end beyond it is not written (ERR_BOUND).  frame_off
+        (n + 1 int64) receives the frame offsets and the total, status_out
+        (int32, n entries, or None) each frame's status, and `results`, a
+        device int64 tensor of n_streams x 4 (one zmqg_zmtp_send_result per
+        stream), is read with zmtp_send_results() once the stream is done."""
+        n_streams, n = int(stream_sid.numel()), int(frame_stream.numel())
+        if out_bytes is None:
+            out_bytes = out.numel() * out.element_size()
+        self._check(_lib.zmqg_encode_zmtp_multi(self._ctx, n_streams, _ptr(stream_sid), n, _ptr(frame_stream),
+                                                _ptr(nonce), _ptr(flags), _ptr(in_off), _ptr(length), _ptr(inp),
+                                                _ptr(out), int(out_bytes), _ptr(frame_off), _ptr(status_out),
+                                                _ptr(results), _stream_handle(stream)), "zmqg_encode_zmtp_multi")
+
+    @staticmethod
+    def zmtp_send_results(results):
+        """encode_zmtp_multi's `results` (synchronised) as a list of dicts, one per stream."""
+        r = results.cpu().numpy().view(np.uint64).reshape(-1, 4)
+        return [dict(frames=int(x[0]), out_off=int(x[1]), out_bytes=int(x[2]),
                      error=int(np.int32(x[3] & np.uint64(0xffffffff)))) for x in r]
 
     # ---- handshake key derivation (device tensors of n x 32 bytes) ----
