@@ -26,6 +26,12 @@
  *   curve_encoding_t::get_and_inc_nonce (_cn_nonce)
  *     src/curve_mechanism_base.hpp:41                ZMQG_OPT_NONCE_AUTO,
  *                                                    zmqg_session_*_nonce
+ *   curve_server_t::process_hello, produce_welcome
+ *     src/curve_server.cpp:117-254                   zmqg_curve_server_hello_batch
+ *   curve_server_t::process_initiate (to ZAP)
+ *     src/curve_server.cpp:256-383                   zmqg_curve_server_initiate_batch
+ *   curve_server_t::produce_ready
+ *     src/curve_server.cpp:419-458                   zmqg_curve_server_ready_batch
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -612,6 +618,111 @@ int zmqg_box_afternm_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *key, const 
 int zmqg_box_open_afternm_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *key, const uint8_t *nonce,
                                 const uint64_t *in_off, const uint32_t *len, const uint8_t *in,
                                 const uint64_t *out_off, uint8_t *out, int32_t *status_out, void *stream);
+
+/* The server side of the CURVE handshake in batches (SURVEY.md section 8f
+ * row 3): curve_server_t's HELLO -> WELCOME and INITIATE -> READY steps
+ * (src/curve_server.cpp:117-458) for many connections per call, with the
+ * reference's contract: the same commands in, the same commands out, the same
+ * ZMQ_PROTOCOL_ERROR_* code for each rejected command, decided in the same
+ * order.  The outputs feed zmqg_session_set_batch_ex as they are.
+ *
+ * Out of scope: the client side (produce_hello, process_welcome,
+ * produce_initiate, process_ready); ZAP and parse_metadata -- the INITIATE
+ * call returns the client's long-term key and the metadata bytes and the host
+ * does the rest, as the reference does between INITIATE and READY
+ * (src/curve_server.cpp:385-416); ERROR commands.
+ *
+ * Conventions of the three calls: asynchronous on `stream`; every pointer is
+ * device-accessible; command bytes may start at any byte alignment, the packed
+ * fixed-size arrays (state, random, welcome_out, client_key_out, precom_out)
+ * are 4-byte aligned; n == 0 returns 0 and does nothing; a null pointer with
+ * n > 0, or n > 2^31 - 1, returns -EINVAL; the host reads nothing back.  A
+ * rejected command is not a call failure: its code is in status_out.
+ *
+ * zmqg_curve_server_hello_batch: process_hello + produce_welcome
+ * (src/curve_server.cpp:117-254).  Item i is the command body
+ * cmd[cmd_off[i] .. +cmd_len[i]).  server_sk is the socket's long-term secret
+ * (_secret_key), common to the batch.  random[96 i ..] supplies what the
+ * reference draws with randombytes (the device has no RNG, and the call is
+ * deterministic): bytes 0..32 s' (the short-term secret, _cn_secret), 32..64
+ * the cookie key (:204), 64..80 the cookie nonce (:194), 80..96 the WELCOME
+ * nonce (:221).  Checks, in this order, the first that fails giving the status:
+ *   1. len <= 1 or len <= cmd[0]                 ZMQG_ERR_MALFORMED_UNSPECIFIED
+ *      (check_basic_command_structure, src/mechanism_base.cpp:14-25)
+ *   2. len < 6 or not "\x05HELLO" (:126)         ZMQG_ERR_UNEXPECTED_COMMAND
+ *   3. len != 200 (:133)                         ZMQG_ERR_MALFORMED_HELLO
+ *   4. cmd[6] != 1 or cmd[7] != 0 (:144)         ZMQG_ERR_MALFORMED_HELLO
+ *   5. the box cmd[120..200) does not open under k1 = crypto_box_beforenm(C' =
+ *      cmd[80..112), server_sk) and nonce "CurveZMQHELLO---" || cmd[112..120)
+ *      (:169)                                    ZMQG_ERR_CRYPTOGRAPHIC
+ *      A C' whose X25519 result is all zero (small order) counts as not
+ *      opening, as libsodium's crypto_box_open does.  The 64 plaintext bytes
+ *      are not inspected; the reference does not inspect them either.
+ * On success status_out[i] = 0; welcome_out[168 i ..] holds the WELCOME command
+ * "\x07WELCOME" || WELCOME nonce || box, the box (:232) under k1 and nonce
+ * "WELCOME-" || WELCOME nonce over S' || cookie nonce || cookie box with S' =
+ * X25519(s', 9) and the cookie box (:208) crypto_secretbox of C' || s' under
+ * the cookie key and nonce "COOKIE--" || cookie nonce; and state[128 i ..]
+ * holds C'(32) | s'(32) | cookie key(32) | precom(32) with precom =
+ * crypto_box_beforenm(C', s'), the connection's _cn_precom.  It is derived
+ * here, where its ladder runs beside the other two, not at INITIATE where the
+ * reference derives it (:382-383); the value is the same.  `state` holds
+ * secrets: the caller owns it and clears it.  On failure the item's WELCOME
+ * slot and state record are zero-filled. */
+#define ZMQG_ERR_KEY_EXCHANGE 0x10000003       /* ZMQ_PROTOCOL_ERROR_ZMTP_KEY_EXCHANGE */
+#define ZMQG_ERR_MALFORMED_HELLO 0x10000013    /* ..._MALFORMED_COMMAND_HELLO */
+#define ZMQG_ERR_MALFORMED_INITIATE 0x10000014 /* ..._MALFORMED_COMMAND_INITIATE */
+#define ZMQG_HS_STATE_BYTES 128
+#define ZMQG_HS_RANDOM_BYTES 96
+#define ZMQG_HS_WELCOME_BYTES 168
+int zmqg_curve_server_hello_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t server_sk[32], const uint64_t *cmd_off,
+                                  const uint32_t *cmd_len, const uint8_t *cmd, const uint8_t *random, uint8_t *state,
+                                  uint8_t *welcome_out, int32_t *status_out, void *stream);
+
+/* zmqg_curve_server_initiate_batch: process_initiate up to the ZAP decision
+ * (src/curve_server.cpp:256-383).  state[128 i ..] is what the HELLO call
+ * wrote for this connection (a gathered array when the batch order differs).
+ * Checks, in this order:
+ *   1. basic structure, as above                 ZMQG_ERR_MALFORMED_UNSPECIFIED
+ *   2. len < 9 or not "\x08INITIATE" (:265)      ZMQG_ERR_UNEXPECTED_COMMAND
+ *   3. len < 257 (:272)                          ZMQG_ERR_MALFORMED_INITIATE
+ *   4. the cookie box cmd[25..105) does not open under state's cookie key and
+ *      nonce "COOKIE--" || cmd[9..25) (:291)     ZMQG_ERR_CRYPTOGRAPHIC
+ *   5. its 64 plaintext bytes differ from state's C' || s' (:302)
+ *                                                ZMQG_ERR_CRYPTOGRAPHIC
+ *   6. the box cmd[113..len) does not open under state's precom and nonce
+ *      "CurveZMQINITIATE" || cmd[105..113) (:334) ZMQG_ERR_CRYPTOGRAPHIC
+ *   7. its plaintext is C(32) || vouch nonce(16) || vouch box(80) || metadata;
+ *      the vouch box does not open under crypto_box_beforenm(C, s') and nonce
+ *      "VOUCH---" || vouch nonce (:359; a small-order C counts as not
+ *      opening)                                  ZMQG_ERR_CRYPTOGRAPHIC
+ *   8. the vouch's first 32 plaintext bytes differ from C' (:370)
+ *                                                ZMQG_ERR_KEY_EXCHANGE
+ * On success status_out[i] = 0, client_key_out[32 i ..] = C (what
+ * send_zap_request receives), precom_out[32 i ..] = precom (packed, so the
+ * array goes to zmqg_session_set_batch_ex as is), peer_nonce_out[i] =
+ * BE64(cmd[105..113)), the value the reference passes to set_peer_nonce (:330)
+ * and that call's peer_nonce entry, meta_len_out[i] = len - 257 and the
+ * metadata bytes (parse_metadata's input, :415) at meta_out[meta_off[i] ..].
+ * On failure the key and precom slots are zero, peer_nonce_out[i] and
+ * meta_len_out[i] are 0 and no byte of meta_out is written.  The INITIATE tag
+ * is verified over the ciphertext before anything is decrypted, and the
+ * metadata is decrypted to meta_out only after check 8 has passed. */
+int zmqg_curve_server_initiate_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *state, const uint64_t *cmd_off,
+                                     const uint32_t *cmd_len, const uint8_t *cmd, uint8_t *client_key_out,
+                                     uint8_t *precom_out, uint64_t *peer_nonce_out, const uint64_t *meta_off,
+                                     uint8_t *meta_out, uint32_t *meta_len_out, int32_t *status_out, void *stream);
+
+/* zmqg_curve_server_ready_batch: produce_ready (src/curve_server.cpp:419-458).
+ * Writes 30 + meta_len[i] bytes at out[out_off[i]] (any alignment): "\x05READY"
+ * || BE64(nonce[i]) || box of meta[meta_off[i] .. +meta_len[i]) under
+ * precom[32 i ..] and nonce "CurveZMQREADY---" || BE64(nonce[i]) (:435-441).
+ * nonce[i] is what get_and_inc_nonce returns there: 1 for a fresh connection,
+ * whose session is then installed with send nonce 2 (zmqg_session_set_batch_ex
+ * above).  Outputs must not overlap each other or `meta`. */
+int zmqg_curve_server_ready_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *precom, const uint64_t *nonce,
+                                  const uint64_t *meta_off, const uint32_t *meta_len, const uint8_t *meta,
+                                  const uint64_t *out_off, uint8_t *out, void *stream);
 
 /* Batched Z85 key codec: zmq_z85_encode /
  * zmq_z85_decode (src/zmq_utils.cpp:100-180, include/zmq.h:537-540) over n

@@ -50,6 +50,7 @@
 #include "curve_device.hpp"
 #include "curve_frames.hpp"
 #include "curve_frames_lds.hpp"
+#include "curve_handshake.hpp"
 #include "curve_msg.hpp"
 #include "curve_z85.hpp"
 #include "curve_x25519.hpp"
@@ -3765,6 +3766,61 @@ int zmqg_box_open_afternm_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *key, c
     ZCHECK(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(k_box<true>, dim3((unsigned) ((n + 63) / 64)), dim3(64), 0, (hipStream_t) stream,
                        (uint32_t) n, key, nonce, in_off, len, in, out_off, out, status_out);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+int zmqg_curve_server_hello_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t server_sk[32], const uint64_t *cmd_off,
+                                  const uint32_t *cmd_len, const uint8_t *cmd, const uint8_t *random, uint8_t *state,
+                                  uint8_t *welcome_out, int32_t *status_out, void *stream)
+{
+    if (!ctx || check_n(n))
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!server_sk || !cmd_off || !cmd_len || !cmd || !random || !state || !welcome_out || !status_out)
+        return -EINVAL;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    // three waves per 64 connections: one per X25519 ladder (curve_handshake.hpp)
+    hipLaunchKernelGGL(k_hs_hello, dim3((unsigned) ((n + 63) / 64)), dim3(kHsHelloThreads), 0, (hipStream_t) stream,
+                       (uint32_t) n, server_sk, cmd_off, cmd_len, cmd, random, state, welcome_out, status_out);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+int zmqg_curve_server_initiate_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *state, const uint64_t *cmd_off,
+                                     const uint32_t *cmd_len, const uint8_t *cmd, uint8_t *client_key_out,
+                                     uint8_t *precom_out, uint64_t *peer_nonce_out, const uint64_t *meta_off,
+                                     uint8_t *meta_out, uint32_t *meta_len_out, int32_t *status_out, void *stream)
+{
+    if (!ctx || check_n(n))
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!state || !cmd_off || !cmd_len || !cmd || !client_key_out || !precom_out || !peer_nonce_out || !meta_off ||
+        !meta_out || !meta_len_out || !status_out)
+        return -EINVAL;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_hs_initiate, dim3((unsigned) ((n + 63) / 64)), dim3(64), 0, (hipStream_t) stream,
+                       (uint32_t) n, state, cmd_off, cmd_len, cmd, client_key_out, precom_out,
+                       (unsigned long long *) peer_nonce_out, meta_off, meta_out, meta_len_out, status_out);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+int zmqg_curve_server_ready_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *precom, const uint64_t *nonce,
+                                  const uint64_t *meta_off, const uint32_t *meta_len, const uint8_t *meta,
+                                  const uint64_t *out_off, uint8_t *out, void *stream)
+{
+    if (!ctx || check_n(n))
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!precom || !nonce || !meta_off || !meta_len || !meta || !out_off || !out)
+        return -EINVAL;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_hs_ready, dim3((unsigned) ((n + 63) / 64)), dim3(64), 0, (hipStream_t) stream, (uint32_t) n,
+                       precom, (const unsigned long long *) nonce, meta_off, meta_len, meta, out_off, out);
     ZCHECK(ctx, hipGetLastError());
     return 0;
 }

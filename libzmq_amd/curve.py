@@ -29,6 +29,11 @@ ERR_INVALID_SEQUENCE = 0x10000002
 ERR_MALFORMED_UNSPECIFIED = 0x10000011
 ERR_MALFORMED_MESSAGE = 0x10000012
 ERR_CRYPTOGRAPHIC = 0x11000001
+# the handshake's (include/zmq.h:427-431)
+ERR_KEY_EXCHANGE = 0x10000003
+ERR_MALFORMED_HELLO = 0x10000013
+ERR_MALFORMED_INITIATE = 0x10000014
+HS_STATE_BYTES, HS_RANDOM_BYTES, HS_WELCOME_BYTES = 128, 96, 168  # ZMQG_HS_*
 # library codes (zmqg_curve.h): unknown session; frame above the caller's max_len
 ERR_SESSION = 0x7A000001
 ERR_BOUND = 0x7A000002
@@ -98,6 +103,9 @@ _lib.zmqg_scalarmult_batch.argtypes = [_P, _U64] + [_P] * 5
 _lib.zmqg_box_beforenm_batch.argtypes = [_P, _U64] + [_P] * 5
 _lib.zmqg_box_afternm_batch.argtypes = [_P, _U64] + [_P] * 8
 _lib.zmqg_box_open_afternm_batch.argtypes = [_P, _U64] + [_P] * 9
+_lib.zmqg_curve_server_hello_batch.argtypes = [_P, _U64] + [_P] * 9
+_lib.zmqg_curve_server_initiate_batch.argtypes = [_P, _U64] + [_P] * 12
+_lib.zmqg_curve_server_ready_batch.argtypes = [_P, _U64] + [_P] * 8
 _lib.zmqg_z85_encode_batch.argtypes = [_P, _U64] + [_P] * 7
 _lib.zmqg_z85_decode_batch.argtypes = [_P, _U64] + [_P] * 7
 _lib.zmqg_host_alloc.argtypes = [_P, _U64, ctypes.POINTER(_P)]
@@ -415,6 +423,42 @@ class CurveContext:
                                                      _ptr(length), _ptr(inp), _ptr(out_off), _ptr(out),
                                                      _ptr(status_out), _stream_handle(stream)),
                     "zmqg_box_open_afternm_batch")
+
+    # ---- the server's handshake steps (curve_server_t), device tensors ----
+    def server_hello_batch(self, server_sk, cmd_off, cmd_len, cmd, random, state, welcome_out, status_out,
+                           stream=None):
+        """process_hello + produce_welcome per item: HELLO command i is
+        cmd[cmd_off[i] .. +cmd_len[i]); server_sk the 32-byte long-term secret
+        (device), random n x 96 bytes (s' | cookie key | cookie nonce | WELCOME
+        nonce).  Fills status_out (0 or ERR_*), welcome_out (n x 168) and state
+        (n x 128: C' | s' | cookie key | precom)."""
+        n = int(status_out.numel())
+        self._check(_lib.zmqg_curve_server_hello_batch(self._ctx, n, _ptr(server_sk), _ptr(cmd_off), _ptr(cmd_len),
+                                                       _ptr(cmd), _ptr(random), _ptr(state), _ptr(welcome_out),
+                                                       _ptr(status_out), _stream_handle(stream)),
+                    "zmqg_curve_server_hello_batch")
+
+    def server_initiate_batch(self, state, cmd_off, cmd_len, cmd, client_key_out, precom_out, peer_nonce_out,
+                              meta_off, meta_out, meta_len_out, status_out, stream=None):
+        """process_initiate up to the ZAP decision per item: `state` as
+        server_hello_batch wrote it.  Fills status_out, client_key_out and
+        precom_out (n x 32), peer_nonce_out (int64, n), meta_len_out (int32, n)
+        and each accepted item's metadata at meta_out[meta_off[i] ..]."""
+        n = int(status_out.numel())
+        self._check(_lib.zmqg_curve_server_initiate_batch(self._ctx, n, _ptr(state), _ptr(cmd_off), _ptr(cmd_len),
+                                                          _ptr(cmd), _ptr(client_key_out), _ptr(precom_out),
+                                                          _ptr(peer_nonce_out), _ptr(meta_off), _ptr(meta_out),
+                                                          _ptr(meta_len_out), _ptr(status_out),
+                                                          _stream_handle(stream)),
+                    "zmqg_curve_server_initiate_batch")
+
+    def server_ready_batch(self, precom, nonce, meta_off, meta_len, meta, out_off, out, stream=None):
+        """produce_ready per item: 30 + meta_len[i] bytes at out[out_off[i]],
+        "\\x05READY" || BE64(nonce[i]) || box of the metadata under precom[i]."""
+        n = int(nonce.numel())
+        self._check(_lib.zmqg_curve_server_ready_batch(self._ctx, n, _ptr(precom), _ptr(nonce), _ptr(meta_off),
+                                                       _ptr(meta_len), _ptr(meta), _ptr(out_off), _ptr(out),
+                                                       _stream_handle(stream)), "zmqg_curve_server_ready_batch")
 
     # ---- batched Z85 (zmq_z85_encode / zmq_z85_decode), device tensors ----
     def z85_encode_batch(self, in_off, length, inp, out_off, out, status_out, stream=None):

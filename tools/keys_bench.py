@@ -3,6 +3,10 @@
 (X25519 + HSalsa20) and crypto_scalarmult_base for N random keys, keys/s;
 handshake boxes (zmqg_box_afternm_batch / _open_) of HELLO (64 B) and
 INITIATE-like (256 B) plaintexts, boxes/s;
+the server's HELLO and INITIATE steps as one call each
+(zmqg_curve_server_hello_batch / _initiate_batch) beside the same steps
+composed from the calls above, handshakes/s, at N and at 1024 connections (an
+accept burst);
 and the CPU reference for scale (libsodium via the oracle's dlopen is not
 exposed, so the oracle's portable C X25519 on one core)."""
 import os
@@ -14,6 +18,139 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from libzmq_amd import curve as C  # noqa: E402
+
+
+def _median_ms(fns, rounds=5, window=0.25):
+    """Median call time in ms of each fn: all warmed up, then `rounds` rounds
+    that alternate between them, each timing enough calls to fill `window` s."""
+    per = []
+    for fn in fns:
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        per.append(max(1, int(window / max(time.perf_counter() - t0, 1e-6))))
+    got = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            for _ in range(per[k]):
+                fn()
+            torch.cuda.synchronize()
+            got[k].append((time.perf_counter() - t0) / per[k] * 1e3)
+    return [float(np.median(g)) for g in got]
+
+
+def handshake_lines(ctx, n):
+    """Server HELLO and INITIATE for n connections, handshakes/s: the one-call
+    forms (zmqg_curve_server_hello_batch / _initiate_batch) and, beside each,
+    the same step composed from the library's other batch calls with their
+    inputs already gathered (only the launches count) -- HELLO: two beforenm,
+    one scalarmult_base, one open, two seals; INITIATE: three opens and one
+    beforenm.  The commands are valid handshakes from the model (256 distinct
+    ones, repeated)."""
+    from tests import curve_handshake_model as M
+    rng = np.random.default_rng(5)
+    server_sk = rng.integers(0, 256, 32, dtype=np.uint8).tobytes()
+    base = [M.random_handshake(rng, server_sk, meta_len=40) for _ in range(min(n, 256))]
+    hs = [base[i % len(base)] for i in range(n)]
+
+    def dev(b):
+        a = np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray)) else np.ascontiguousarray(b)
+        if a.dtype == np.uint64:
+            a = a.view(np.int64)
+        elif a.dtype == np.uint32:
+            a = a.view(np.int32)
+        return torch.from_numpy(a.copy()).cuda()
+
+    u8 = lambda size: torch.zeros(size, dtype=torch.uint8, device="cuda")
+    st = torch.zeros(n, dtype=torch.int32, device="cuda")
+    idx = np.arange(n, dtype=np.uint64)
+    # ---- HELLO
+    sk = dev(server_sk)
+    cmd = dev(b"".join(h["hello"] for h in hs))
+    off, ln = dev(idx * 200), dev(np.full(n, 200, np.uint32))
+    rnd = dev(b"".join(h["random"] for h in hs))
+    state, wel = u8(128 * n), u8(168 * n)
+    fused_hello = lambda: ctx.server_hello_batch(sk, off, ln, cmd, rnd, state, wel, st)
+    cpk = dev(b"".join(h["hello"][80:112] for h in hs))
+    ssk = dev(server_sk * n)
+    sps = dev(b"".join(h["random"][:32] for h in hs))
+    k1, spk, pre = u8(32 * n), u8(32 * n), u8(32 * n)
+    hbox = dev(b"".join(h["hello"][120:200] for h in hs))
+    hnonce = dev(b"".join(b"CurveZMQHELLO---" + h["hello"][112:120] for h in hs))
+    cnonce = dev(b"".join(b"COOKIE--" + h["random"][64:80] for h in hs))
+    wnonce = dev(b"".join(b"WELCOME-" + h["random"][80:96] for h in hs))
+    ckey = dev(b"".join(h["random"][32:64] for h in hs))
+    cplain = dev(b"".join(h["state"][:64] for h in hs))
+    wplain = dev(rng.integers(0, 256, 128 * n, dtype=np.uint8))
+    hplain, cbox, wbox = u8(64 * n), u8(80 * n), u8(144 * n)
+    o64, o80, o128, o144 = dev(idx * 64), dev(idx * 80), dev(idx * 128), dev(idx * 144)
+    l64, l80, l128 = (dev(np.full(n, v, np.uint32)) for v in (64, 80, 128))
+
+    def composed_hello():
+        ctx.box_beforenm_batch(cpk, ssk, k1, st)
+        ctx.scalarmult_batch(sps, None, spk, st)
+        ctx.box_beforenm_batch(cpk, sps, pre, st)
+        ctx.box_open_afternm_batch(k1, hnonce, o80, l80, hbox, o64, hplain, st)
+        ctx.box_afternm_batch(ckey, cnonce, o64, l64, cplain, o80, cbox)
+        ctx.box_afternm_batch(k1, wnonce, o128, l128, wplain, o144, wbox)
+
+    fused_hello()
+    composed_hello()
+    torch.cuda.synchronize()
+    assert bool((st == 0).all())
+    assert wel.cpu().numpy().tobytes() == b"".join(h["welcome"] for h in hs)
+    # ---- INITIATE
+    istate = dev(b"".join(h["state"] for h in hs))
+    ilen = len(hs[0]["initiate"])
+    icmd = dev(b"".join(h["initiate"] for h in hs))
+    ioff, iln = dev(idx * ilen), dev(np.full(n, ilen, np.uint32))
+    ck, ipre, meta = u8(32 * n), u8(32 * n), u8(40 * n)
+    peer = torch.zeros(n, dtype=torch.int64, device="cuda")
+    mlen = torch.zeros(n, dtype=torch.int32, device="cuda")
+    moff = dev(idx * 40)
+    fused_initiate = lambda: ctx.server_initiate_batch(istate, ioff, iln, icmd, ck, ipre, peer, moff, meta, mlen, st)
+    blen = ilen - 113
+    cookie = dev(b"".join(h["initiate"][25:105] for h in hs))
+    cn2 = dev(b"".join(b"COOKIE--" + h["initiate"][9:25] for h in hs))
+    ibox = dev(b"".join(h["initiate"][113:] for h in hs))
+    inonce = dev(b"".join(b"CurveZMQINITIATE" + h["initiate"][105:113] for h in hs))
+    pkey = dev(b"".join(h["precom"] for h in hs))
+    plains = [O_open(h) for h in hs[:len(base)]]
+    plains = [plains[i % len(base)] for i in range(n)]
+    cc = dev(b"".join(p[:32] for p in plains))
+    vbox = dev(b"".join(p[48:128] for p in plains))
+    vnonce = dev(b"".join(b"VOUCH---" + p[32:48] for p in plains))
+    kv, cpl, ipl, vpl = u8(32 * n), u8(64 * n), u8((blen - 16) * n), u8(64 * n)
+    ob, lb, op = dev(idx * blen), dev(np.full(n, blen, np.uint32)), dev(idx * (blen - 16))
+
+    def composed_initiate():
+        ctx.box_open_afternm_batch(ckey, cn2, o80, l80, cookie, o64, cpl, st)
+        ctx.box_open_afternm_batch(pkey, inonce, ob, lb, ibox, op, ipl, st)
+        ctx.box_beforenm_batch(cc, sps, kv, st)
+        ctx.box_open_afternm_batch(kv, vnonce, o80, l80, vbox, o64, vpl, st)
+
+    fused_initiate()
+    torch.cuda.synchronize()
+    assert bool((st == 0).all()) and ipre.cpu().numpy().tobytes() == b"".join(h["precom"] for h in hs)
+    composed_initiate()
+    torch.cuda.synchronize()
+    assert bool((st == 0).all())
+    for name, fused, composed in (("server HELLO", fused_hello, composed_hello),
+                                  ("server INITIATE", fused_initiate, composed_initiate)):
+        f, c = _median_ms([fused, composed])
+        print(f"{name:16s} {n} conns  one call {f:8.3f} ms {n / f / 1e3:8.3f} M handshakes/s   "
+              f"composed {c:8.3f} ms {n / c / 1e3:8.3f} M/s   ratio {c / f:5.2f}")
+
+
+def O_open(h):
+    """The INITIATE box's plaintext of a model handshake (C | vouch | metadata)."""
+    from oracle import oracle as O
+    rc, plain = O.box_open_easy_afternm(h["initiate"][113:], b"CurveZMQINITIATE" + h["initiate"][105:113], h["precom"])
+    assert rc == 0
+    return plain
 
 
 def main():
@@ -58,6 +195,8 @@ def main():
             dt = (time.perf_counter() - t0) / reps
             print(f"{name:16s} {n} boxes {dt * 1e3:8.3f} ms  {n / dt / 1e6:6.2f} M boxes/s")
         assert bool((st == 0).all()) and torch.equal(back, m)
+    for hn in sorted({n, 1024}):
+        handshake_lines(ctx, hn)
     from oracle import oracle as O
     m = 200
     t0 = time.perf_counter()
