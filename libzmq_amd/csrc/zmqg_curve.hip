@@ -90,6 +90,7 @@ constexpr int kBodyThreads = 256; // 4 waves x 2 tile buffers of 9 KiB: 2 workgr
 constexpr int kHeadThreads = 256;
 constexpr uint32_t kMaxFrameStream = 64 * 72; // frames up to 4.5 KiB of stream: frame kernel
 constexpr int kFixupThreads = 256;
+constexpr uint32_t kReplayMaxSessions = 8192; // the replay tables' limit; more sessions take the sort fallback
 
 // Per-frame records written by the head kernel and read by the body kernel,
 // grouped by when a body lane needs them so each group is one batch of
@@ -127,178 +128,11 @@ struct __attribute__((aligned(16))) FrameFin { // tag / status inputs (64 B)
 };
 static_assert(sizeof(FrameFin) == 64, "FrameFin layout");
 
-struct Workspace {
-    uint64_t cap = 0; // frames
-    FrameHot *hot = nullptr;
-    FramePow *pw = nullptr;
-    FrameFin *fin = nullptr;
-    uint32_t *powtab = nullptr;   // [cap][kMaxPow][5], entries k >= kPowInline
-    unsigned long long *acc = nullptr; // [cap][5]
-    uint32_t *cnt = nullptr;      // [cap]
-    uint32_t *nch = nullptr;      // [cap]
-    uint32_t *chunk_end = nullptr; // [cap]
-    unsigned long long *v = nullptr;     // [cap] accepted nonce or 0
-    unsigned long long *excl = nullptr;  // [cap]
-    unsigned long long *v_s = nullptr;   // [cap] sorted
-    unsigned long long *excl_s = nullptr; // [cap]
-    uint32_t *iota = nullptr;     // [cap]
-    uint32_t *perm = nullptr;     // [cap]
-    uint32_t *keys_s = nullptr;   // [cap]
-    uint8_t *last = nullptr;      // [cap] last frame of its session in the batch
-    uint32_t *list_frame = nullptr;      // [cap] big-frame list: frame index at each position
-    PostOp *post = nullptr;              // [cap] decode: k_post's zero fills and in-place moves
-    unsigned long long *psnap = nullptr; // [cap] session peer nonce before the batch, per frame
-    unsigned long long *blockmax = nullptr; // [cap] frame-kernel workgroup maxima of vout
-    ZState *zs = nullptr;                   // call state carried from call to call (on the device)
-    unsigned long long *lb_flag = nullptr;  // [cap] look-back state per workgroup ticket
-    unsigned long long *lb_agg = nullptr;   // [cap]
-    unsigned long long *lb_inc = nullptr;   // [cap]
-    unsigned long long *lb_rec = nullptr;   // [2 kFramesBS] k_frames_seq's one-round look-back records
-    void *temp = nullptr;
-    size_t temp_bytes = 0;
-    unsigned long long *rt = nullptr; // replay tables: [tiles][S] then [row blocks][S] (also the nonce tables)
-    uint64_t *nonce = nullptr;        // [cap] ZMQG_OPT_NONCE_AUTO over several sessions: each frame's nonce
-    size_t rt_cap = 0;
-    uint8_t *stage = nullptr;         // ZMQG_OPT_VERIFY_FIRST: decoded payloads before the verdict copy
-    size_t stage_cap = 0;
-    bool use_last = false; // the last replay ran the sort fallback (k_fixup writes the peer nonces)
-};
-
 } // namespace
 
-namespace {
-// The synchronous zmqg_decode_zmtp's result, written by the decode into
-// mapped host memory.
-struct ZmtpResHost {
-    zmqg_zmtp_result r;
-};
+#include "curve_ctx.hpp" // zmqg_ctx and its buffers, ZCHECK, the stream ordering
 
-// device buffers of the ZMTP framing calls
-struct ZmtpWs {
-    uint64_t n_cap = 0;                   // send side: frames
-    uint64_t *F = nullptr;                // [n_cap + 1] frame bytes
-    uint64_t *wire_off = nullptr;         // [n_cap] body offsets
-    uint64_t g_cap = 0;                   // receive side: 16 KiB workgroups of the stream
-    uint64_t c_cap = 0;                   // receive side: candidates
-    uint64_t f_cap = 0;                   // receive side: frames (max_frames)
-    uint64_t *cand_wg = nullptr;          // [g_cap * kZmtpWgCap] each workgroup's candidates, in order
-    uint64_t *count_wg = nullptr;         // [g_cap + 1]
-    uint64_t *off_wg = nullptr;           // [g_cap + 1] exclusive sum of count_wg
-    uint16_t *count16 = nullptr;          // [g_cap + 8] count_wg as 16-bit fields (k_zmtp_compact sums them)
-    uint64_t *cand = nullptr;             // [c_cap] sorted candidates
-    uint64_t *cdesc = nullptr;            // [c_cap] their frames: body offset | body length << 32
-    uint8_t *cflag = nullptr;             // [c_cap] their flags bytes
-    uint64_t *nb = nullptr;               // [c_cap] next unlinked candidate in the 256-candidate segment
-    uint64_t *first_w = nullptr;          // [g_cap + 1] first unlinked candidate in workgroup lists >= w
-    uint32_t *wid = nullptr;              // [c_cap] each candidate's workgroup list
-    uint64_t *run = nullptr;              // [2 (f_cap + 1)]
-    uint64_t *runpre = nullptr;           // [f_cap + 1]
-    uint32_t *sid_fill = nullptr;         // [f_cap]
-    uint8_t *fflags = nullptr;            // [f_cap]
-    ZmtpWalk *walk = nullptr;
-    ZmtpResHost *res = nullptr;           // the synchronous call's result, mapped host memory
-    ZmtpResHost *res_dev = nullptr;       // (its device address)
-    void *temp = nullptr;
-    size_t temp_bytes = 0;
-    uint64_t s_cap = 0;                   // zmqg_encode_zmtp_multi: frames
-    uint32_t *s_sid = nullptr;            // [s_cap] the session each frame is encoded on (or none)
-    uint64_t *s_woff = nullptr;           // [s_cap] body offsets
-    unsigned long long *s_tab = nullptr;  // [tiles][streams], [row blocks][streams], bases and totals [2][streams]
-    size_t s_tab_cap = 0;
-};
-} // namespace
-
-struct zmqg_ctx {
-    int device = 0;
-    int cus = 256; // compute units of the device (one persistent body workgroup each)
-    uint32_t max_sessions = 0;
-    int sort_bits = 0;
-    DevSession *sessions = nullptr;
-    unsigned long long *peer = nullptr; // [max_sessions]
-    unsigned long long *send = nullptr; // [max_sessions] send nonces (_cn_nonce) for ZMQG_OPT_NONCE_AUTO
-    unsigned long long *zero_peer = nullptr; // [max_sessions] zeros: ZMQG_OPT_REPLAY_HOST's peer snapshot
-    Workspace ws;
-    ZmtpWs zw;
-    // host staging for the *_host entry points
-    uint8_t *pin = nullptr;
-    size_t pin_bytes = 0;
-    uint8_t *mpin = nullptr, *mpin_dev = nullptr; // the per-message buffer (zmqg_*_msg), device-mapped
-    size_t mpin_bytes = 0;
-    // zmqg_session_set_batch: device-mapped descriptors of the last install,
-    // free again once `sinst_done` is reached
-    uint8_t *sinst = nullptr, *sinst_dev = nullptr;
-    size_t sinst_bytes = 0;
-    hipEvent_t sinst_done = nullptr;
-    hipEvent_t order_ev = nullptr; // zmqg_*_msg: own_stream waits for the last batch stream's work
-    uint8_t *dbuf = nullptr;
-    size_t dbuf_bytes = 0;
-    hipStream_t own_stream = nullptr;
-    // the stream of the last batch call (the session accessors and the
-    // per-message calls order after it); has_last tells "none yet" from the
-    // null stream, which is a stream like any other here
-    hipStream_t last_stream = nullptr;
-    bool has_last = false;
-    std::vector<uint8_t> h_downgrade; // host copy of each session's downgrade_sub
-    // profiling: event pairs per kind, recycled through a pool
-    bool profiling = false;
-    int frames_cap[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // decode frame-kernel workgroups resident at once, G = 1,
-                                                     // 2, 4, seq, lds, split 2, 4, 8, seq under STREAM_OUT
-    int force_g = -1;                 // ZMQG_FRAMES_G: frame-kernel variant override (experiments)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof[6];
-    std::vector<hipEvent_t> event_pool;
-    // completion fences of the asynchronous host path: (id, event) pending,
-    // events recycled through fence_pool
-    std::vector<std::pair<uint64_t, hipEvent_t>> fences;
-    std::vector<hipEvent_t> fence_pool;
-    // zmqg_fence_record_notify: ids whose host function has run (a fence
-    // found there is reached whatever its event says), and the host
-    // functions enqueued and not yet finished
-    std::mutex notify_mu;
-    std::vector<uint64_t> notified;
-    std::atomic<int> notify_pending{0};
-    uint64_t fence_ctr = 0;
-    std::mutex fence_mu;
-    char last_error[256] = {0};
-    std::mutex mu;
-};
-
-#define ZCHECK(ctx, expr)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            snprintf((ctx)->last_error, sizeof((ctx)->last_error), "%s:%d %s: %s", __FILE__,   \
-                     __LINE__, #expr, hipGetErrorString(e_));                                  \
-            return -EIO;                                                               \
-        }                                                                                      \
-    } while (0)
-
-// The ctx's work is ordered by stream: a batch call runs on the caller's
-// stream (which then becomes the ctx's last stream); every call that uses
-// the ctx's workspace or sessions on another stream than the last one --
-// the batch calls, the session installs and accessors, the per-message
-// calls -- first makes it wait for everything queued on the last one (an
-// event recorded there, order_after_last; nothing when the stream is the
-// same).  The null stream is a stream like any other: with own_stream
-// non-blocking it is not ordered implicitly.
 static int notify_wait(zmqg_ctx *ctx);
-
-static void set_last(zmqg_ctx *ctx, hipStream_t st)
-{
-    ctx->last_stream = st;
-    ctx->has_last = true;
-}
-
-static int order_after_last(zmqg_ctx *ctx, hipStream_t st)
-{
-    if (ctx->has_last && ctx->last_stream != st) {
-        if (!ctx->order_ev)
-            ZCHECK(ctx, hipEventCreateWithFlags(&ctx->order_ev, hipEventDisableTiming));
-        ZCHECK(ctx, hipEventRecord(ctx->order_ev, ctx->last_stream));
-        ZCHECK(ctx, hipStreamWaitEvent(st, ctx->order_ev, 0));
-    }
-    set_last(ctx, st);
-    return 0;
-}
 
 // =====================================================================
 // device helpers
@@ -884,7 +718,7 @@ __global__ __launch_bounds__(256) void k_session_max(uint32_t n, const uint32_t 
 //                     tile's prefix row in LDS: excl = table[sid] (plus, when
 //                     a session repeats within the 64, the max of its earlier
 //                     lanes), then table[sid] = max(table[sid], v)
-constexpr uint32_t kReplayMaxSessions = 8192, kReplayRB = 64, kReplayMaxTiles = 4096;
+constexpr uint32_t kReplayRB = 64, kReplayMaxTiles = 4096;
 
 __global__ __launch_bounds__(256) void k_replay_tiles(uint32_t n, uint32_t T, uint32_t S,
                                                      const uint32_t *__restrict__ sid,
@@ -2024,16 +1858,7 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
 // =====================================================================
 namespace {
 
-template <typename T>
-int grow(zmqg_ctx *ctx, T *&p, size_t count, hipStream_t st)
-{
-    if (p)
-        ZCHECK(ctx, hipFreeAsync(p, st));
-    p = nullptr;
-    ZCHECK(ctx, hipMallocAsync((void **) &p, count * sizeof(T) + 64, st));
-    return 0;
-}
-
+// the call state's first value (ensure_workspace, once per ctx)
 __global__ void k_zstate_init(ZState *zs)
 {
     if (threadIdx.x == 0) {
@@ -2043,78 +1868,10 @@ __global__ void k_zstate_init(ZState *zs)
     }
 }
 
-// Workspace for n frames, grown in stream order on the batch's stream: the
-// old buffers are freed and the new ones allocated and initialised on `st`,
-// after the work already queued there (no device-wide synchronisation).
-int ensure_workspace(zmqg_ctx *ctx, uint64_t n, hipStream_t st)
-{
-    Workspace &w = ctx->ws;
-    if (n > w.cap) {
-        uint64_t cap = w.cap ? w.cap : 1024;
-        while (cap < n)
-            cap *= 2;
-        int rc;
-        if ((rc = grow(ctx, w.hot, cap, st)) || (rc = grow(ctx, w.pw, cap, st)) || (rc = grow(ctx, w.fin, cap, st)) ||
-            (rc = grow(ctx, w.powtab, cap * kMaxPow * 5, st)) ||
-            (rc = grow(ctx, w.acc, cap * 5, st)) || (rc = grow(ctx, w.cnt, cap, st)) || (rc = grow(ctx, w.nch, cap, st)) ||
-            (rc = grow(ctx, w.chunk_end, cap, st)) || (rc = grow(ctx, w.v, cap, st)) || (rc = grow(ctx, w.excl, cap, st)) ||
-            (rc = grow(ctx, w.v_s, cap, st)) || (rc = grow(ctx, w.excl_s, cap, st)) || (rc = grow(ctx, w.iota, cap, st)) ||
-            (rc = grow(ctx, w.perm, cap, st)) || (rc = grow(ctx, w.keys_s, cap, st)) || (rc = grow(ctx, w.last, cap, st)) ||
-            (rc = grow(ctx, w.list_frame, cap, st)) || (rc = grow(ctx, w.post, cap, st)) ||
-            (rc = grow(ctx, w.psnap, cap, st)) || (rc = grow(ctx, w.blockmax, cap, st)) ||
-            (rc = grow(ctx, w.lb_flag, cap, st)) || (rc = grow(ctx, w.lb_agg, cap, st)) || (rc = grow(ctx, w.lb_inc, cap, st)) ||
-            (rc = grow(ctx, w.lb_rec, 2 * kFramesBS, st)) || (rc = grow(ctx, w.nonce, cap, st)))
-            return rc;
-        ZCHECK(ctx, hipMemsetAsync(w.lb_flag, 0, cap * sizeof(unsigned long long), st));
-        ZCHECK(ctx, hipMemsetAsync(w.lb_rec, 0, 2 * kFramesBS * sizeof(unsigned long long), st)); // (no record valid)
-        if (!w.zs) {
-            if ((rc = grow(ctx, w.zs, 1, st)))
-                return rc;
-            hipLaunchKernelGGL(k_zstate_init, dim3(1), dim3(64), 0, st, w.zs);
-            ZCHECK(ctx, hipGetLastError());
-        }
-        w.cap = cap;
-    }
-    // hipCUB temporaries for n frames
-    size_t need = 0, b = 0;
-    const int nn = (int) n;
-    if (ctx->sort_bits > 0 && ctx->max_sessions > kReplayMaxSessions) { // the sort fallback of replay_multi
-        b = 0;
-        ZCHECK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const uint32_t *) nullptr, w.keys_s,
-                                                        (const uint32_t *) nullptr, w.perm, nn, 0, ctx->sort_bits));
-        need = b > need ? b : need;
-        b = 0;
-        ZCHECK(ctx, hipcub::DeviceScan::ExclusiveScanByKey(nullptr, b, w.keys_s, w.v_s, w.excl_s, hipcub::Max(),
-                                                            0ull, nn));
-        need = b > need ? b : need;
-    }
-    if (need > w.temp_bytes) {
-        size_t cap = w.temp_bytes ? w.temp_bytes : 4096;
-        while (cap < need)
-            cap *= 2;
-        if (w.temp)
-            ZCHECK(ctx, hipFreeAsync(w.temp, st));
-        w.temp = nullptr;
-        ZCHECK(ctx, hipMallocAsync(&w.temp, cap, st));
-        w.temp_bytes = cap;
-    }
-    return 0;
-}
-
 uint32_t body_grid(const zmqg_ctx *ctx)
 {
     // persistent: kBodyWgPerCu workgroups of 4 waves per compute unit
     return kBodyWgPerCu * (ctx->cus > 0 ? (uint32_t) ctx->cus : 256u);
-}
-
-// ZMQG_OPT_REPLAY_HOST: a zeroed peer-nonce table for the frame kernels
-int ensure_zero_peer(zmqg_ctx *ctx, hipStream_t st)
-{
-    if (ctx->zero_peer)
-        return 0;
-    ZCHECK(ctx, hipMallocAsync((void **) &ctx->zero_peer, sizeof(unsigned long long) * ctx->max_sessions, st));
-    ZCHECK(ctx, hipMemsetAsync(ctx->zero_peer, 0, sizeof(unsigned long long) * ctx->max_sessions, st));
-    return 0;
 }
 
 int check_n(uint64_t n)
@@ -2315,13 +2072,7 @@ int nonce_multi(zmqg_ctx *ctx, uint32_t nn, const uint32_t *sid, hipStream_t st,
         T = replay_tile_frames(nn, S);
     const uint32_t tiles = (nn + T - 1) / T, rbs = (tiles + kReplayRB - 1) / kReplayRB;
     const size_t need = ((size_t) tiles + rbs + 1) * S; // tables, block sums, send snapshot
-    if (need > w.rt_cap) {
-        if (w.rt)
-            ZCHECK(ctx, hipFreeAsync(w.rt, st));
-        w.rt = nullptr;
-        ZCHECK(ctx, hipMallocAsync((void **) &w.rt, need * sizeof(unsigned long long), st));
-        w.rt_cap = need;
-    }
+    ZRESERVE(ctx, w.rt, need, st);
     unsigned long long *tab = w.rt, *blk = w.rt + (size_t) tiles * S, *snap = blk + (size_t) rbs * S;
     hipLaunchKernelGGL(k_nonce_tiles, dim3(tiles), dim3(256), S * sizeof(uint32_t), st, nn, T, S, sid, tab);
     ZCHECK(ctx, hipGetLastError());
@@ -2350,13 +2101,7 @@ int replay_multi(zmqg_ctx *ctx, uint32_t nn, const uint32_t *sid, hipStream_t st
         const uint32_t T = replay_tile_frames(nn, S);
         const uint32_t tiles = (nn + T - 1) / T, rbs = (tiles + kReplayRB - 1) / kReplayRB;
         const size_t need = ((size_t) tiles + rbs + 1) * S; // tables, block sums, send snapshot
-        if (need > w.rt_cap) {
-            if (w.rt)
-                ZCHECK(ctx, hipFreeAsync(w.rt, st));
-            w.rt = nullptr;
-            ZCHECK(ctx, hipMallocAsync((void **) &w.rt, need * sizeof(unsigned long long), st));
-            w.rt_cap = need;
-        }
+        ZRESERVE(ctx, w.rt, need, st);
         unsigned long long *tab = w.rt, *blk = w.rt + (size_t) tiles * S;
         hipLaunchKernelGGL(k_replay_tiles, dim3(tiles), dim3(256), S * sizeof(unsigned long long), st, nn, T, S, sid,
                            (const unsigned long long *) w.v, tab);
@@ -2374,13 +2119,13 @@ int replay_multi(zmqg_ctx *ctx, uint32_t nn, const uint32_t *sid, hipStream_t st
         return 0;
     }
     const dim3 hgrid((nn + kHeadThreads - 1) / kHeadThreads);
-    size_t tb = w.temp_bytes;
-    ZCHECK(ctx, hipcub::DeviceRadixSort::SortPairs(w.temp, tb, sid, w.keys_s, w.iota, w.perm, (int) nn, 0,
+    size_t tb = w.temp.count;
+    ZCHECK(ctx, hipcub::DeviceRadixSort::SortPairs(w.temp.p, tb, sid, w.keys_s.p, w.iota.p, w.perm.p, (int) nn, 0,
                                                     ctx->sort_bits, st));
     hipLaunchKernelGGL(k_gather_u64, hgrid, dim3(kHeadThreads), 0, st, nn, w.perm, w.v, w.v_s);
     ZCHECK(ctx, hipGetLastError());
-    tb = w.temp_bytes;
-    ZCHECK(ctx, hipcub::DeviceScan::ExclusiveScanByKey(w.temp, tb, w.keys_s, w.v_s, w.excl_s, hipcub::Max(),
+    tb = w.temp.count;
+    ZCHECK(ctx, hipcub::DeviceScan::ExclusiveScanByKey(w.temp.p, tb, w.keys_s.p, w.v_s.p, w.excl_s.p, hipcub::Max(),
                                                         0ull, (int) nn, hipcub::Equality(), st));
     hipLaunchKernelGGL(k_scatter_replay, hgrid, dim3(kHeadThreads), 0, st, nn, w.perm, w.keys_s, w.excl_s, w.excl,
                        w.last);
@@ -2485,24 +2230,17 @@ int zmqg_ctx_destroy(zmqg_ctx *ctx)
         (void) hipStreamSynchronize(ctx->last_stream);
     if (ctx->own_stream)
         (void) hipStreamSynchronize(ctx->own_stream);
-    Workspace &w = ctx->ws;
-    void *ptrs[] = {w.hot, w.pw, w.fin, w.powtab, w.acc, w.cnt, w.nch, w.chunk_end, w.v, w.excl, w.v_s,
-                    w.excl_s, w.iota, w.perm, w.keys_s, w.last, w.list_frame, w.post, w.psnap, w.blockmax, w.zs,
-                    w.lb_flag, w.lb_agg, w.lb_inc, w.lb_rec, w.temp, w.rt, w.nonce, w.stage, ctx->sessions, ctx->peer, ctx->send, ctx->zero_peer, ctx->dbuf};
-    for (void *p : ptrs)
-        if (p)
-            (void) hipFree(p);
-    {
-        ZmtpWs &z = ctx->zw;
-        void *zp[] = {z.F,      z.wire_off, z.cand_wg, z.count_wg, z.off_wg, z.cand, z.nb,   z.first_w,
-                      z.wid,    z.run,      z.runpre,  z.sid_fill, z.fflags, z.walk, z.temp, z.count16, z.cdesc, z.cflag,
-                      z.s_sid,  z.s_woff,   z.s_tab};
-        for (void *p : zp)
-            if (p)
-                (void) hipFree(p);
-        if (z.res)
-            (void) hipHostFree(z.res);
-    }
+    ctx->mem.free_all(); // every stream-ordered buffer; below, what is not
+    if (ctx->sessions)
+        (void) hipFree(ctx->sessions);
+    if (ctx->peer)
+        (void) hipFree(ctx->peer);
+    if (ctx->send)
+        (void) hipFree(ctx->send);
+    if (ctx->dbuf)
+        (void) hipFree(ctx->dbuf);
+    if (ctx->zw.res)
+        (void) hipHostFree(ctx->zw.res);
     if (ctx->pin)
         (void) hipHostFree(ctx->pin);
     if (ctx->mpin)
@@ -2936,14 +2674,7 @@ static int decode_batch_impl(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, con
     uint8_t *const out_user = out;
     if (verify_first) {
         // the staging area mirrors `out`: same offsets, same alignment mod 16
-        const size_t need = out_bytes + 16;
-        if (need > w.stage_cap) {
-            if (w.stage)
-                ZCHECK(ctx, hipFreeAsync(w.stage, st));
-            w.stage = nullptr;
-            ZCHECK(ctx, hipMallocAsync((void **) &w.stage, need, st));
-            w.stage_cap = need;
-        }
+        ZRESERVE(ctx, w.stage, out_bytes + 16, st);
         out = w.stage + ((uintptr_t) out_user & 15u);
     }
     const uint32_t nn = (uint32_t) n;
@@ -3017,7 +2748,7 @@ static int decode_batch_impl(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, con
                            w.pw, w.fin, w.powtab, flags_out, status_out, w.acc, w.cnt, w.excl, w.psnap, w.post, zflags);
         ZCHECK(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_post, dim3(body_grid(ctx)), dim3(256), 0, st, w.zs, (const PostOp *) w.post,
-                           (uint8_t *) w.powtab);
+                           (uint8_t *) w.powtab.p);
         ZCHECK(ctx, hipGetLastError());
         body.end();
     }
@@ -3149,9 +2880,7 @@ static int msg_stage(zmqg_ctx *ctx, size_t bytes)
 {
     if (bytes <= ctx->mpin_bytes)
         return 0;
-    size_t cap = ctx->mpin_bytes ? ctx->mpin_bytes : 65536;
-    while (cap < bytes)
-        cap *= 2;
+    const size_t cap = grown_cap(ctx->mpin_bytes, 65536, bytes);
     if (ctx->mpin)
         ZCHECK(ctx, hipHostFree(ctx->mpin));
     ctx->mpin = nullptr;
@@ -3353,40 +3082,6 @@ int zmqg_decode_host(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, const uint6
     return 0;
 }
 
-static int zmtp_temp(zmqg_ctx *ctx, size_t need, hipStream_t st)
-{
-    ZmtpWs &z = ctx->zw;
-    if (need <= z.temp_bytes)
-        return 0;
-    size_t cap = z.temp_bytes ? z.temp_bytes : 4096;
-    while (cap < need)
-        cap *= 2;
-    if (z.temp)
-        ZCHECK(ctx, hipFreeAsync(z.temp, st));
-    z.temp = nullptr;
-    z.temp_bytes = 0;
-    ZCHECK(ctx, hipMallocAsync(&z.temp, cap, st));
-    z.temp_bytes = cap;
-    return 0;
-}
-
-// the receive side's per-frame buffers for n frames (under ctx->mu)
-static int zmtp_frame_cap(zmqg_ctx *ctx, uint64_t n, hipStream_t st)
-{
-    ZmtpWs &z = ctx->zw;
-    if (n <= z.f_cap)
-        return 0;
-    uint64_t cap = z.f_cap ? z.f_cap : 1024;
-    while (cap < n)
-        cap *= 2;
-    int rc;
-    if ((rc = grow(ctx, z.run, 2 * (cap + 1), st)) || (rc = grow(ctx, z.runpre, cap + 1, st)) ||
-        (rc = grow(ctx, z.sid_fill, cap, st)) || (rc = grow(ctx, z.fflags, cap, st)))
-        return rc;
-    z.f_cap = cap;
-    return 0;
-}
-
 int zmqg_encode_zmtp(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, const uint64_t *nonce, const uint8_t *flags,
                      const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
                      uint64_t *frame_off, void *stream)
@@ -3402,25 +3097,22 @@ int zmqg_encode_zmtp(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, const uint6
     if (!sid || !nonce || !flags || !in_off || !len || !in || !out)
         return -EINVAL;
     ZmtpWs &z = ctx->zw;
-    int rc;
     if (n > z.n_cap) {
-        uint64_t cap = z.n_cap ? z.n_cap : 1024;
-        while (cap < n)
-            cap *= 2;
-        if ((rc = grow(ctx, z.F, cap + 1, st)) || (rc = grow(ctx, z.wire_off, cap, st)))
-            return rc;
+        const uint64_t cap = grown_cap(z.n_cap, 1024, n);
+        z.n_cap = 0;
+        ZRESERVE(ctx, z.F, cap + 1, st);
+        ZRESERVE(ctx, z.wire_off, cap, st);
         z.n_cap = cap;
     }
     size_t need = 0;
-    ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, z.F, frame_off, (int) (n + 1), st));
-    if ((rc = zmtp_temp(ctx, need, st)))
-        return rc;
+    ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, z.F.p, frame_off, (int) (n + 1), st));
+    ZRESERVE(ctx, z.temp, grown_cap(z.temp.count, 4096, need), st);
     const unsigned g1 = (unsigned) ((n + 1 + 255) / 256), g0 = (unsigned) ((n + 255) / 256);
     hipLaunchKernelGGL(k_zmtp_sizes, dim3(g1), dim3(256), 0, st, n, sid, flags, len, ctx->sessions,
                        ctx->max_sessions, z.F);
     ZCHECK(ctx, hipGetLastError());
-    size_t tb = z.temp_bytes;
-    ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(z.temp, tb, z.F, frame_off, (int) (n + 1), st));
+    size_t tb = z.temp.count;
+    ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(z.temp.p, tb, z.F.p, frame_off, (int) (n + 1), st));
     hipLaunchKernelGGL(k_zmtp_headers, dim3(g0), dim3(256), 0, st, n, frame_off, out, z.wire_off);
     ZCHECK(ctx, hipGetLastError());
     return zmqg_encode_batch(ctx, n, sid, nonce, flags, in_off, len, in, z.wire_off, out, stream);
@@ -3472,23 +3164,14 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
     if ((rc = order_after_last(ctx, st)))
         return rc;
     if (n > z.s_cap) {
-        uint64_t cap = z.s_cap ? z.s_cap : 1024;
-        while (cap < n)
-            cap *= 2;
-        if ((rc = grow(ctx, z.s_sid, cap, st)) || (rc = grow(ctx, z.s_woff, cap, st)))
-            return rc;
+        const uint64_t cap = grown_cap(z.s_cap, 1024, n);
+        z.s_cap = 0;
+        ZRESERVE(ctx, z.s_sid, cap, st);
+        ZRESERVE(ctx, z.s_woff, cap, st);
         z.s_cap = cap;
     }
     const size_t need = ((size_t) tiles + rbs + 2) * NS; // tables, block sums, bases, totals
-    if (need > z.s_tab_cap) {
-        size_t cap = z.s_tab_cap ? z.s_tab_cap : 4096;
-        while (cap < need)
-            cap *= 2;
-        z.s_tab_cap = 0;
-        if ((rc = grow(ctx, z.s_tab, cap, st)))
-            return rc;
-        z.s_tab_cap = cap;
-    }
+    ZRESERVE(ctx, z.s_tab, grown_cap(z.s_tab.count, 4096, need), st);
     unsigned long long *tab = z.s_tab, *blk = tab + (size_t) tiles * NS, *base = blk + (size_t) rbs * NS,
                        *tot = base + NS;
     const dim3 cg((NS + 255) / 256, rbs);
@@ -3548,30 +3231,30 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
     int rc;
     const uint64_t nwg = (in_bytes + kZmtpWgBytes - 1) / kZmtpWgBytes;
     if (nwg > z.g_cap) {
-        uint64_t cap = z.g_cap ? z.g_cap : 64;
-        while (cap < nwg)
-            cap *= 2;
-        if ((rc = grow(ctx, z.cand_wg, cap * kZmtpWgCap, st)) || (rc = grow(ctx, z.count_wg, cap + 1, st)) ||
-            (rc = grow(ctx, z.off_wg, cap + 1, st)) || (rc = grow(ctx, z.first_w, cap + 1, st)) ||
-            (rc = grow(ctx, z.count16, cap + 8, st)))
-            return rc;
+        const uint64_t cap = grown_cap(z.g_cap, 64, nwg);
+        z.g_cap = 0;
+        ZRESERVE(ctx, z.cand_wg, cap * kZmtpWgCap, st);
+        ZRESERVE(ctx, z.count_wg, cap + 1, st);
+        ZRESERVE(ctx, z.off_wg, cap + 1, st);
+        ZRESERVE(ctx, z.first_w, cap + 1, st);
+        ZRESERVE(ctx, z.count16, cap + 8, st);
         z.g_cap = cap;
     }
     // candidates: signatures are >= 8 bytes apart, one candidate each
     const uint64_t ccap = in_bytes / 8 + 2;
     if (ccap > z.c_cap) {
-        uint64_t cap = z.c_cap ? z.c_cap : 1024;
-        while (cap < ccap)
-            cap *= 2;
-        if ((rc = grow(ctx, z.cand, cap, st)) || (rc = grow(ctx, z.nb, cap, st)) || (rc = grow(ctx, z.wid, cap, st)) ||
-            (rc = grow(ctx, z.cdesc, cap, st)) || (rc = grow(ctx, z.cflag, cap, st)))
-            return rc;
+        const uint64_t cap = grown_cap(z.c_cap, 1024, ccap);
+        z.c_cap = 0;
+        ZRESERVE(ctx, z.cand, cap, st);
+        ZRESERVE(ctx, z.nb, cap, st);
+        ZRESERVE(ctx, z.wid, cap, st);
+        ZRESERVE(ctx, z.cdesc, cap, st);
+        ZRESERVE(ctx, z.cflag, cap, st);
         z.c_cap = cap;
     }
     if ((rc = zmtp_frame_cap(ctx, max_frames, st)))
         return rc;
-    if (!z.walk && (rc = grow(ctx, z.walk, 1, st)))
-        return rc;
+    ZRESERVE(ctx, z.walk, 1, st);
     const uint32_t g = (uint32_t) nwg;
     // persistent grids over device-side counts: enough workgroups to cover
     // config-2-sized streams in one pass
@@ -3590,12 +3273,11 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
     const bool inline_sum = nwg <= kZmtpInlineSumLists && !getenv("ZMQG_ZMTP_CUB");
     if (!inline_sum) {
         size_t need = 0;
-        ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, z.count_wg, z.off_wg, (int) (nwg + 1), st));
-        if ((rc = zmtp_temp(ctx, need, st)))
-            return rc;
+        ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, z.count_wg.p, z.off_wg.p, (int) (nwg + 1), st));
+        ZRESERVE(ctx, z.temp, grown_cap(z.temp.count, 4096, need), st);
         ZCHECK(ctx, hipMemsetAsync(z.count_wg + nwg, 0, sizeof(uint64_t), st));
-        size_t tb = z.temp_bytes;
-        ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(z.temp, tb, z.count_wg, z.off_wg, (int) (nwg + 1), st));
+        size_t tb = z.temp.count;
+        ZCHECK(ctx, hipcub::DeviceScan::ExclusiveSum(z.temp.p, tb, z.count_wg.p, z.off_wg.p, (int) (nwg + 1), st));
     }
     hipLaunchKernelGGL(k_zmtp_compact, dim3((g + kZmtpCompactLists - 1) / kZmtpCompactLists), dim3(kZmtpThreads), 0, st, in, in_bytes, (const uint64_t *) z.cand_wg,
                        (const uint64_t *) z.count_wg, inline_sum ? (const uint16_t *) z.count16 : nullptr, z.off_wg,
@@ -3613,7 +3295,7 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
                        (const uint8_t *) z.cflag, m_p,
                        (const uint64_t *) z.run, (const uint64_t *) z.runpre, (const ZmtpWalk *) z.walk, max_frames,
                        frame_in_off, frame_len, z.fflags, z.sid_fill, sid, out_off,
-                       (unsigned long long *) ((char *) z.walk + offsetof(ZmtpWalk, out_bytes)));
+                       (unsigned long long *) ((char *) z.walk.p + offsetof(ZmtpWalk, out_bytes)));
     ZCHECK(ctx, hipGetLastError());
     // the decode over max_frames (the empty frames fail as malformed and
     // write nothing else); a maxmsgsize within the frame kernel's range bounds
