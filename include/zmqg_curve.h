@@ -32,6 +32,12 @@
  *     src/curve_server.cpp:256-383                   zmqg_curve_server_initiate_batch
  *   curve_server_t::produce_ready
  *     src/curve_server.cpp:419-458                   zmqg_curve_server_ready_batch
+ *   crypto_box_keypair, produce_hello
+ *     src/curve_client_tools.hpp:230-234, :29-65     zmqg_curve_client_hello_batch
+ *   process_welcome, produce_initiate
+ *     src/curve_client_tools.hpp:67-199              zmqg_curve_client_welcome_batch
+ *   curve_client_t::process_ready (to parse_metadata)
+ *     src/curve_client.cpp:179-214                   zmqg_curve_client_ready_batch
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -626,11 +632,13 @@ int zmqg_box_open_afternm_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *key, c
  * ZMQ_PROTOCOL_ERROR_* code for each rejected command, decided in the same
  * order.  The outputs feed zmqg_session_set_batch_ex as they are.
  *
- * Out of scope: the client side (produce_hello, process_welcome,
- * produce_initiate, process_ready); ZAP and parse_metadata -- the INITIATE
- * call returns the client's long-term key and the metadata bytes and the host
- * does the rest, as the reference does between INITIATE and READY
- * (src/curve_server.cpp:385-416); ERROR commands.
+ * The client side is the block after this one (zmqg_curve_client_*_batch).
+ *
+ * Out of scope: the state machine (which command to send or expect when);
+ * ZAP and parse_metadata -- the INITIATE call returns the client's long-term
+ * key and the metadata bytes and the host does the rest, as the reference
+ * does between INITIATE and READY (src/curve_server.cpp:385-416); ERROR
+ * commands.
  *
  * Conventions of the three calls: asynchronous on `stream`; every pointer is
  * device-accessible; command bytes may start at any byte alignment, the packed
@@ -723,6 +731,109 @@ int zmqg_curve_server_initiate_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *s
 int zmqg_curve_server_ready_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *precom, const uint64_t *nonce,
                                   const uint64_t *meta_off, const uint32_t *meta_len, const uint8_t *meta,
                                   const uint64_t *out_off, uint8_t *out, void *stream);
+
+/* The client side of the CURVE handshake in batches: curve_client_t's HELLO,
+ * WELCOME -> INITIATE and READY steps (src/curve_client.cpp:112-214,
+ * src/curve_client_tools.hpp:29-199) for many connections per call -- a
+ * process that dials many CURVE peers.  The commands are the reference's byte
+ * for byte, and a rejected command gets the code the reference reports.  The
+ * outputs feed zmqg_session_set_batch_ex as they are; the client's session is
+ * installed with send nonce 3 (see that call's comment) and READY's peer nonce.
+ *
+ * Out of scope: the state machine, ZAP (a server matter), parse_metadata --
+ * the READY call returns the metadata bytes -- and ERROR commands.  The caller
+ * dispatches by command name, as process_handshake_command does
+ * (src/curve_client.cpp:65-78): a READY or ERROR command passed to the WELCOME
+ * call is "unexpected" there.
+ *
+ * Conventions as for the three server calls: asynchronous on `stream`; every
+ * pointer is device-accessible; command bytes (cmd, meta, out, meta_out) may
+ * start at any byte alignment, the packed fixed-size arrays (server_pk,
+ * cn_secret, state, hello_out, client_pk, client_sk, vouch_nonce, precom,
+ * precom_out) are 4-byte aligned; n == 0 returns 0 and does nothing; a null
+ * pointer with n > 0, or n > 2^31 - 1, returns -EINVAL; the host reads nothing
+ * back.  A rejected command is not a call failure: its code is in status_out.
+ * The device has no RNG: what the reference draws with randombytes comes in as
+ * an argument, and each call is deterministic.
+ *
+ * zmqg_curve_client_hello_batch: crypto_box_keypair
+ * (src/curve_client_tools.hpp:230-234) + produce_hello (:29-65,
+ * src/curve_client.cpp:112-131).  server_pk[32 i ..] is connection i's server
+ * long-term key S (per item: a dialling process talks to many servers),
+ * cn_secret[32 i ..] the 32 random bytes of the short-term secret c' (used as
+ * given; X25519 clamps them), nonce[i] what get_and_inc_nonce returns, 1 on a
+ * fresh connection.  Per item C' = X25519(c', 9), k1 = crypto_box_beforenm(S,
+ * c') and the box of 64 zero bytes under k1 and nonce "CurveZMQHELLO---" ||
+ * BE64(nonce).  On success status_out[i] = 0, hello_out[200 i ..] =
+ * "\x05HELLO" 01 00 | 72 zero bytes | C' | BE64(nonce) | box(80) and
+ * state[128 i ..] = C'(32) | c'(32) | k1(32) | S(32).  Where X25519(c', S) is
+ * all zero (a small-order S) crypto_box fails and the reference reports
+ * ZMQ_PROTOCOL_ERROR_ZMTP_CRYPTOGRAPHIC (src/curve_client.cpp:118-120):
+ * status_out[i] = ZMQG_ERR_CRYPTOGRAPHIC and the item's HELLO slot and state
+ * record are zero-filled.  `state` holds secrets: the caller owns it and
+ * clears it. */
+#define ZMQG_ERR_MALFORMED_READY 0x10000016 /* ..._MALFORMED_COMMAND_READY */
+#define ZMQG_HS_HELLO_BYTES 200
+#define ZMQG_HS_CLIENT_STATE_BYTES 128
+int zmqg_curve_client_hello_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *server_pk, const uint8_t *cn_secret,
+                                  const uint64_t *nonce, uint8_t *state, uint8_t *hello_out, int32_t *status_out,
+                                  void *stream);
+
+/* zmqg_curve_client_welcome_batch: process_welcome + produce_initiate
+ * (src/curve_client_tools.hpp:67-199, src/curve_client.cpp:133-177), which the
+ * reference runs back to back.  state[128 i ..] is what the HELLO call wrote;
+ * client_pk / client_sk[32 i ..] the long-term pair C, c; item i's command is
+ * cmd[cmd_off[i] .. +cmd_len[i]); vouch_nonce[16 i ..] the 16 random bytes of
+ * :137; nonce[i] INITIATE's nonce, 2 on a fresh connection; the client's
+ * metadata (as add_basic_properties produces it; any length, 0 included) is
+ * meta[meta_off[i] .. +meta_len[i]).  Checks, in this order, the first that
+ * fails giving the status:
+ *   1. len < 8 or not "\x07WELCOME"               ZMQG_ERR_UNEXPECTED_COMMAND
+ *      (is_handshake_command, :286-290; nothing is read from an empty
+ *      command; the client does not call check_basic_command_structure)
+ *   2. len != 168 (:75)                           ZMQG_ERR_CRYPTOGRAPHIC
+ *      (the reference reports CRYPTOGRAPHIC for every process_welcome
+ *      failure, src/curve_client.cpp:139-141, not MALFORMED_WELCOME)
+ *   3. the box cmd[24..168) does not open under state's k1 and nonce
+ *      "WELCOME-" || cmd[8..24) (:92)             ZMQG_ERR_CRYPTOGRAPHIC
+ *   4. its plaintext is S'(32) || cookie(96); X25519(c', S') is all zero (a
+ *      small-order S' inside a valid box)         ZMQG_ERR_CRYPTOGRAPHIC
+ *      Deviation: the reference zmq_asserts there (:105-106) and aborts the
+ *      process; a batch call reports the connection instead.
+ * On success status_out[i] = 0, precom_out[32 i ..] = crypto_box_beforenm(S',
+ * c') (packed, so the array goes to zmqg_session_set_batch_ex and to the READY
+ * call as is) and 257 + meta_len[i] bytes are written at out[out_off[i]]:
+ * "\x08INITIATE" | cookie(96) | BE64(nonce) | box, the box (:177) under precom
+ * and nonce "CurveZMQINITIATE" || BE64(nonce) over C | vouch_nonce | vouch
+ * box(80) | metadata, the vouch box (:140) that of C' || S under
+ * crypto_box_beforenm(S', c) and nonce "VOUCH---" || vouch_nonce.  On failure
+ * the precom slot is zero and no byte of `out` is written (every verdict is
+ * known before the first seal).  Outputs must not overlap each other, `cmd`
+ * or `meta`; 257 + meta_len[i] must fit 32 bits. */
+int zmqg_curve_client_welcome_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *state, const uint8_t *client_pk,
+                                    const uint8_t *client_sk, const uint64_t *cmd_off, const uint32_t *cmd_len,
+                                    const uint8_t *cmd, const uint8_t *vouch_nonce, const uint64_t *nonce,
+                                    const uint64_t *meta_off, const uint32_t *meta_len, const uint8_t *meta,
+                                    const uint64_t *out_off, uint8_t *out, uint8_t *precom_out, int32_t *status_out,
+                                    void *stream);
+
+/* zmqg_curve_client_ready_batch: process_ready up to parse_metadata
+ * (src/curve_client.cpp:179-214).  Checks, in this order:
+ *   1. len < 6 or not "\x05READY"                 ZMQG_ERR_UNEXPECTED_COMMAND
+ *   2. len < 30                                   ZMQG_ERR_MALFORMED_READY
+ *   3. the box cmd[14..len) does not open under precom[32 i ..] and nonce
+ *      "CurveZMQREADY---" || cmd[6..14)           ZMQG_ERR_CRYPTOGRAPHIC
+ *      (the tag is verified over the whole ciphertext before any byte is
+ *      decrypted)
+ * On success status_out[i] = 0, peer_nonce_out[i] = BE64(cmd[6..14)), the value
+ * :204 passes to set_peer_nonce and zmqg_session_set_batch_ex's peer_nonce
+ * entry, meta_len_out[i] = len - 30 and the metadata bytes (parse_metadata's
+ * input) are at meta_out[meta_off[i] ..].  On failure both are 0 and no byte
+ * of meta_out is written. */
+int zmqg_curve_client_ready_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *precom, const uint64_t *cmd_off,
+                                  const uint32_t *cmd_len, const uint8_t *cmd, uint64_t *peer_nonce_out,
+                                  const uint64_t *meta_off, uint8_t *meta_out, uint32_t *meta_len_out,
+                                  int32_t *status_out, void *stream);
 
 /* Batched Z85 key codec: zmq_z85_encode /
  * zmq_z85_decode (src/zmq_utils.cpp:100-180, include/zmq.h:537-540) over n

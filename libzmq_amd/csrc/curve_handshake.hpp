@@ -9,8 +9,9 @@
 //   k_hs_ready     curve_server_t::produce_ready (src/curve_server.cpp:419-458)
 //
 // Not here: the client side (produce_hello, process_welcome, produce_initiate,
-// process_ready), ZAP and parse_metadata (the host does them between INITIATE
-// and READY, as the reference does), and ERROR commands.
+// process_ready) is curve_handshake_client.hpp, built on the helpers below;
+// ZAP and parse_metadata (the host does them between INITIATE and READY, as
+// the reference does) and ERROR commands are in neither.
 //
 // Work split.  A HELLO needs three X25519 ladders that do not depend on each
 // other -- X25519(server_sk, C') for the HELLO / WELCOME key, X25519(s', 9) for

@@ -51,6 +51,7 @@
 #include "curve_frames.hpp"
 #include "curve_frames_lds.hpp"
 #include "curve_handshake.hpp"
+#include "curve_handshake_client.hpp"
 #include "curve_msg.hpp"
 #include "curve_z85.hpp"
 #include "curve_x25519.hpp"
@@ -3503,6 +3504,68 @@ int zmqg_curve_server_ready_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *prec
     ZCHECK(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(k_hs_ready, dim3((unsigned) ((n + 63) / 64)), dim3(64), 0, (hipStream_t) stream, (uint32_t) n,
                        precom, (const unsigned long long *) nonce, meta_off, meta_len, meta, out_off, out);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+int zmqg_curve_client_hello_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *server_pk, const uint8_t *cn_secret,
+                                  const uint64_t *nonce, uint8_t *state, uint8_t *hello_out, int32_t *status_out,
+                                  void *stream)
+{
+    if (!ctx || check_n(n))
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!server_pk || !cn_secret || !nonce || !state || !hello_out || !status_out)
+        return -EINVAL;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    // two waves per 64 connections: one per X25519 ladder (curve_handshake_client.hpp)
+    hipLaunchKernelGGL(k_hc_hello, dim3((unsigned) ((n + 63) / 64)), dim3(kHcThreads), 0, (hipStream_t) stream,
+                       (uint32_t) n, server_pk, cn_secret, (const unsigned long long *) nonce, state, hello_out,
+                       status_out);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+int zmqg_curve_client_welcome_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *state, const uint8_t *client_pk,
+                                    const uint8_t *client_sk, const uint64_t *cmd_off, const uint32_t *cmd_len,
+                                    const uint8_t *cmd, const uint8_t *vouch_nonce, const uint64_t *nonce,
+                                    const uint64_t *meta_off, const uint32_t *meta_len, const uint8_t *meta,
+                                    const uint64_t *out_off, uint8_t *out, uint8_t *precom_out, int32_t *status_out,
+                                    void *stream)
+{
+    if (!ctx || check_n(n))
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!state || !client_pk || !client_sk || !cmd_off || !cmd_len || !cmd || !vouch_nonce || !nonce || !meta_off ||
+        !meta_len || !meta || !out_off || !out || !precom_out || !status_out)
+        return -EINVAL;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_hc_welcome, dim3((unsigned) ((n + 63) / 64)), dim3(kHcThreads), 0, (hipStream_t) stream,
+                       (uint32_t) n, state, client_pk, client_sk, cmd_off, cmd_len, cmd, vouch_nonce,
+                       (const unsigned long long *) nonce, meta_off, meta_len, meta, out_off, out, precom_out,
+                       status_out);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+int zmqg_curve_client_ready_batch(zmqg_ctx *ctx, uint64_t n, const uint8_t *precom, const uint64_t *cmd_off,
+                                  const uint32_t *cmd_len, const uint8_t *cmd, uint64_t *peer_nonce_out,
+                                  const uint64_t *meta_off, uint8_t *meta_out, uint32_t *meta_len_out,
+                                  int32_t *status_out, void *stream)
+{
+    if (!ctx || check_n(n))
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!precom || !cmd_off || !cmd_len || !cmd || !peer_nonce_out || !meta_off || !meta_out || !meta_len_out ||
+        !status_out)
+        return -EINVAL;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_hc_ready, dim3((unsigned) ((n + 63) / 64)), dim3(64), 0, (hipStream_t) stream, (uint32_t) n,
+                       precom, cmd_off, cmd_len, cmd, (unsigned long long *) peer_nonce_out, meta_off, meta_out,
+                       meta_len_out, status_out);
     ZCHECK(ctx, hipGetLastError());
     return 0;
 }

@@ -34,6 +34,9 @@ ERR_KEY_EXCHANGE = 0x10000003
 ERR_MALFORMED_HELLO = 0x10000013
 ERR_MALFORMED_INITIATE = 0x10000014
 HS_STATE_BYTES, HS_RANDOM_BYTES, HS_WELCOME_BYTES = 128, 96, 168  # ZMQG_HS_*
+# the client's (include/zmq.h:433)
+ERR_MALFORMED_READY = 0x10000016
+HS_HELLO_BYTES, HS_CLIENT_STATE_BYTES = 200, 128
 # library codes (zmqg_curve.h): unknown session; frame above the caller's max_len
 ERR_SESSION = 0x7A000001
 ERR_BOUND = 0x7A000002
@@ -106,6 +109,9 @@ _lib.zmqg_box_open_afternm_batch.argtypes = [_P, _U64] + [_P] * 9
 _lib.zmqg_curve_server_hello_batch.argtypes = [_P, _U64] + [_P] * 9
 _lib.zmqg_curve_server_initiate_batch.argtypes = [_P, _U64] + [_P] * 12
 _lib.zmqg_curve_server_ready_batch.argtypes = [_P, _U64] + [_P] * 8
+_lib.zmqg_curve_client_hello_batch.argtypes = [_P, _U64] + [_P] * 7
+_lib.zmqg_curve_client_welcome_batch.argtypes = [_P, _U64] + [_P] * 16
+_lib.zmqg_curve_client_ready_batch.argtypes = [_P, _U64] + [_P] * 10
 _lib.zmqg_z85_encode_batch.argtypes = [_P, _U64] + [_P] * 7
 _lib.zmqg_z85_decode_batch.argtypes = [_P, _U64] + [_P] * 7
 _lib.zmqg_host_alloc.argtypes = [_P, _U64, ctypes.POINTER(_P)]
@@ -459,6 +465,45 @@ class CurveContext:
         self._check(_lib.zmqg_curve_server_ready_batch(self._ctx, n, _ptr(precom), _ptr(nonce), _ptr(meta_off),
                                                        _ptr(meta_len), _ptr(meta), _ptr(out_off), _ptr(out),
                                                        _stream_handle(stream)), "zmqg_curve_server_ready_batch")
+
+    # ---- the client's handshake steps (curve_client_t), device tensors ----
+    def client_hello_batch(self, server_pk, cn_secret, nonce, state, hello_out, status_out, stream=None):
+        """crypto_box_keypair + produce_hello per item: server_pk and cn_secret
+        n x 32 bytes (S and the random bytes of c'), nonce int64 n.  Fills
+        status_out (0 or ERR_CRYPTOGRAPHIC), hello_out (n x 200) and state
+        (n x 128: C' | c' | k1 | S)."""
+        n = int(status_out.numel())
+        self._check(_lib.zmqg_curve_client_hello_batch(self._ctx, n, _ptr(server_pk), _ptr(cn_secret), _ptr(nonce),
+                                                       _ptr(state), _ptr(hello_out), _ptr(status_out),
+                                                       _stream_handle(stream)), "zmqg_curve_client_hello_batch")
+
+    def client_welcome_batch(self, state, client_pk, client_sk, cmd_off, cmd_len, cmd, vouch_nonce, nonce, meta_off,
+                             meta_len, meta, out_off, out, precom_out, status_out, stream=None):
+        """process_welcome + produce_initiate per item: `state` as
+        client_hello_batch wrote it, WELCOME command i is cmd[cmd_off[i] ..
+        +cmd_len[i]), client_pk / client_sk n x 32, vouch_nonce n x 16, nonce
+        int64 n, the metadata meta[meta_off[i] .. +meta_len[i]).  Fills
+        status_out, precom_out (n x 32) and each accepted item's INITIATE
+        (257 + meta_len[i] bytes) at out[out_off[i] ..]."""
+        n = int(status_out.numel())
+        self._check(_lib.zmqg_curve_client_welcome_batch(self._ctx, n, _ptr(state), _ptr(client_pk), _ptr(client_sk),
+                                                         _ptr(cmd_off), _ptr(cmd_len), _ptr(cmd), _ptr(vouch_nonce),
+                                                         _ptr(nonce), _ptr(meta_off), _ptr(meta_len), _ptr(meta),
+                                                         _ptr(out_off), _ptr(out), _ptr(precom_out),
+                                                         _ptr(status_out), _stream_handle(stream)),
+                    "zmqg_curve_client_welcome_batch")
+
+    def client_ready_batch(self, precom, cmd_off, cmd_len, cmd, peer_nonce_out, meta_off, meta_out, meta_len_out,
+                           status_out, stream=None):
+        """process_ready up to parse_metadata per item: READY command i is
+        cmd[cmd_off[i] .. +cmd_len[i]), precom n x 32.  Fills status_out,
+        peer_nonce_out (int64, n), meta_len_out (int32, n) and each accepted
+        item's metadata at meta_out[meta_off[i] ..]."""
+        n = int(status_out.numel())
+        self._check(_lib.zmqg_curve_client_ready_batch(self._ctx, n, _ptr(precom), _ptr(cmd_off), _ptr(cmd_len),
+                                                       _ptr(cmd), _ptr(peer_nonce_out), _ptr(meta_off),
+                                                       _ptr(meta_out), _ptr(meta_len_out), _ptr(status_out),
+                                                       _stream_handle(stream)), "zmqg_curve_client_ready_batch")
 
     # ---- batched Z85 (zmq_z85_encode / zmq_z85_decode), device tensors ----
     def z85_encode_batch(self, in_off, length, inp, out_off, out, status_out, stream=None):

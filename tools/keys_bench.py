@@ -6,7 +6,8 @@ INITIATE-like (256 B) plaintexts, boxes/s;
 the server's HELLO and INITIATE steps as one call each
 (zmqg_curve_server_hello_batch / _initiate_batch) beside the same steps
 composed from the calls above, handshakes/s, at N and at 1024 connections (an
-accept burst);
+accept burst), and the client's HELLO and WELCOME -> INITIATE steps
+(zmqg_curve_client_hello_batch / _welcome_batch) in the same way;
 and the CPU reference for scale (libsodium via the oracle's dlopen is not
 exposed, so the oracle's portable C X25519 on one core)."""
 import os
@@ -48,8 +49,11 @@ def handshake_lines(ctx, n):
     the same step composed from the library's other batch calls with their
     inputs already gathered (only the launches count) -- HELLO: two beforenm,
     one scalarmult_base, one open, two seals; INITIATE: three opens and one
-    beforenm.  The commands are valid handshakes from the model (256 distinct
-    ones, repeated)."""
+    beforenm.  Then the client's HELLO and WELCOME -> INITIATE
+    (zmqg_curve_client_hello_batch / _welcome_batch) the same way -- HELLO:
+    one scalarmult_base, one beforenm, one seal; WELCOME: one open, two
+    beforenm, two seals.  The commands are valid handshakes from the model
+    (256 distinct ones, repeated)."""
     from tests import curve_handshake_model as M
     rng = np.random.default_rng(5)
     server_sk = rng.integers(0, 256, 32, dtype=np.uint8).tobytes()
@@ -138,8 +142,65 @@ def handshake_lines(ctx, n):
     composed_initiate()
     torch.cuda.synchronize()
     assert bool((st == 0).all())
+    # ---- client HELLO: composed = scalarmult_base, beforenm, one seal
+    from tests import curve_client_model as CM
+    srv = dev(b"".join(h["server_pk"] for h in hs))
+    cns = dev(b"".join(h["cn_sk"] for h in hs))
+    one = dev(np.ones(n, np.uint64))
+    cstate, chello = u8(128 * n), u8(200 * n)
+    fused_chello = lambda: ctx.client_hello_batch(srv, cns, one, cstate, chello, st)
+    cpub, k1c, zeros64, hbox_out = u8(32 * n), u8(32 * n), u8(64 * n), u8(80 * n)
+
+    def composed_chello():
+        ctx.scalarmult_batch(cns, None, cpub, st)
+        ctx.box_beforenm_batch(srv, cns, k1c, st)
+        ctx.box_afternm_batch(k1c, hnonce, o64, l64, zeros64, o80, hbox_out)
+
+    fused_chello()
+    composed_chello()
+    torch.cuda.synchronize()
+    assert bool((st == 0).all())
+    assert chello.cpu().numpy().tobytes() == b"".join(h["hello"] for h in hs)
+    assert hbox_out.cpu().numpy().tobytes() == b"".join(h["hello"][120:] for h in hs)
+    # ---- client WELCOME -> INITIATE: composed = one open, two beforenm, two seals
+    cstates = [CM.client_state(h) for h in base]
+    wstate = dev(b"".join(cstates[i % len(base)] for i in range(n)))
+    lpk, lsk = dev(b"".join(h["client_pk"] for h in hs)), dev(b"".join(h["client_sk"] for h in hs))
+    wcmd, woff, wln = dev(b"".join(h["welcome"] for h in hs)), dev(idx * 168), dev(np.full(n, 168, np.uint32))
+    vn = dev(b"".join(p[32:48] for p in plains))
+    two = dev(np.full(n, 2, np.uint64))
+    cmeta, ml40 = dev(b"".join(h["meta"] for h in hs)), dev(np.full(n, 40, np.uint32))
+    iout, cpre = u8(ilen * n), u8(32 * n)
+    fused_cwelcome = lambda: ctx.client_welcome_batch(wstate, lpk, lsk, woff, wln, wcmd, vn, two, moff, ml40, cmeta,
+                                                      ioff, iout, cpre, st)
+    k1s = dev(b"".join(cstates[i % len(base)][64:96] for i in range(n)))
+    wbox_in = dev(b"".join(h["welcome"][24:] for h in hs))
+    wnonce_c = dev(b"".join(b"WELCOME-" + h["welcome"][8:24] for h in hs))
+    snpk = dev(b"".join(h["sn_pk"] for h in hs))
+    vplain = dev(b"".join(s[0:32] + s[96:128] for s in (cstates[i % len(base)] for i in range(n))))
+    iplain = dev(b"".join(plains))
+    l144 = dev(np.full(n, 144, np.uint32))
+    lp = dev(np.full(n, blen - 16, np.uint32))
+    wpl, pre_c, kv_c, vbox_o, ibox_o = u8(128 * n), u8(32 * n), u8(32 * n), u8(80 * n), u8(blen * n)
+
+    def composed_cwelcome():
+        ctx.box_open_afternm_batch(k1s, wnonce_c, o144, l144, wbox_in, o128, wpl, st)
+        ctx.box_beforenm_batch(snpk, cns, pre_c, st)
+        ctx.box_beforenm_batch(snpk, lsk, kv_c, st)
+        ctx.box_afternm_batch(kv_c, vnonce, o64, l64, vplain, o80, vbox_o)
+        ctx.box_afternm_batch(pre_c, inonce, op, lp, iplain, ob, ibox_o)
+
+    fused_cwelcome()
+    torch.cuda.synchronize()
+    assert bool((st == 0).all()) and iout.cpu().numpy().tobytes() == b"".join(h["initiate"] for h in hs)
+    assert cpre.cpu().numpy().tobytes() == b"".join(h["precom"] for h in hs)
+    composed_cwelcome()
+    torch.cuda.synchronize()
+    assert bool((st == 0).all()) and ibox_o.cpu().numpy().tobytes() == b"".join(h["initiate"][113:] for h in hs)
     for name, fused, composed in (("server HELLO", fused_hello, composed_hello),
-                                  ("server INITIATE", fused_initiate, composed_initiate)):
+                                  ("server INITIATE", fused_initiate, composed_initiate),
+                                  ("client HELLO", fused_chello, composed_chello),
+                                  ("client WELCOME", fused_cwelcome, composed_cwelcome)):
         f, c = _median_ms([fused, composed])
         print(f"{name:16s} {n} conns  one call {f:8.3f} ms {n / f / 1e3:8.3f} M handshakes/s   "
               f"composed {c:8.3f} ms {n / c / 1e3:8.3f} M/s   ratio {c / f:5.2f}")
