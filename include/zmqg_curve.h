@@ -38,6 +38,11 @@
  *     src/curve_client_tools.hpp:67-199              zmqg_curve_client_welcome_batch
  *   curve_client_t::process_ready (to parse_metadata)
  *     src/curve_client.cpp:179-214                   zmqg_curve_client_ready_batch
+ *   ws_decoder_t + curve_mechanism_base_t::decode
+ *     src/ws_decoder.cpp:39-249,
+ *     src/ws_engine.cpp:887-915                      zmqg_decode_ws_multi
+ *   curve_encoding_t::encode + ws_encoder_t
+ *     src/ws_encoder.cpp:26-126                      zmqg_encode_ws_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -578,6 +583,106 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
                            const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
                            uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
                            zmqg_zmtp_send_result *results, void *stream);
+
+/* WebSocket framing (ZWS 2.0 over RFC 6455): the reference's second caller of
+ * the mechanism, ws_engine_t::decode_and_push (src/ws_engine.cpp:887-915),
+ * whose frames come from ws_decoder_t / ws_encoder_t (src/ws_engine.cpp:
+ * 221-250) in place of the ZMTP ones.
+ *
+ * zmqg_decode_ws_multi: zmqg_decode_zmtp_multi with ws_decoder_t's framing
+ * (src/ws_decoder.cpp:39-249).  Everything zmqg_decode_zmtp_multi states about
+ * streams, slots and their order of replay, two streams on one session,
+ * stream_sid[s] >= max_sessions, empty slots, n_streams == 0, max_frames == 0,
+ * the -EINVAL cases, asynchrony, alignment, isolation of the streams and
+ * `out` == `in` holds here.  The framing, from offset 0 of each stream, in the
+ * decoder's own order over the bytes that are present -- a check whose
+ * deciding bytes are all in the stream is made; the first one whose bytes are
+ * not leaves the frame for the next call, consumed staying at the frame's
+ * first byte (a lone last byte 0x02 is an error, a lone 0x82 is incomplete):
+ *   1. byte 0: FIN (0x80) set and the opcode (low 4 bits) 2 binary, 8 close,
+ *      9 ping or 10 pong, else error = EPROTO (:41-63); RSV bits are ignored.
+ *   2. byte 1: the MASK bit equals must_mask (the decoder's !_client: a
+ *      server's receive side is masked), else EPROTO (:72-75); the low 7 bits
+ *      are the size, or 126: two bytes big endian follow, or 127: eight bytes
+ *      (:77-128); non-minimal forms are accepted as the reference accepts them.
+ *   3. with must_mask, the 4-byte masking key (:131-144).
+ *   4. a binary frame: size 0 gives EPROTO (:83-84, :104-105, :122-123,
+ *      :136-137); then one flags byte (XORed with key byte 0), bit 1 = msg_t
+ *      MORE, bit 2 = COMMAND (:146-163, src/ws_protocol.hpp:23-27); the size
+ *      drops by one.
+ *   5. with max_msg_size >= 0 a size above it gives EMSGSIZE (:166-173; for a
+ *      binary frame the size after step 4); so does a size above 2^32 - 1 (this
+ *      library's restriction, as on the ZMTP calls).
+ *   6. `size` body bytes; with must_mask body byte i of a binary frame is
+ *      XORed with key[(i + 1) % 4], of a control frame with key[i % 4]
+ *      (:234-243).
+ * EPROTO is this library's choice (the reference's decoder returns -1 there
+ * and sets no errno).  An error ends the stream's parse: the frames before it
+ * are returned and consumed ends at the failing frame's first byte.
+ * A binary frame takes the next slot of its stream: frame_in_off = out_off =
+ * the absolute offset of its body (the byte behind the flags byte), frame_len
+ * the body size; the unmasked body is decoded as curve_mechanism_base_t::decode
+ * would (src/ws_engine.cpp:895), flags_out / status_out as for
+ * zmqg_decode_batch with the frame's MORE / COMMAND bits ORed into flags_out,
+ * the payload at the body's start.  A binary frame that is not a MESSAGE
+ * command (shorter than 8 bytes, or not starting with "\x07MESSAGE" once
+ * unmasked) is returned as its stream's last frame with the mechanism's
+ * status.  A close, ping or pong frame takes no slot and is not given to the
+ * mechanism (src/ws_engine.cpp:891-894): it ends the stream's parse, consumed
+ * includes it, and results[s].ctl_opcode / ctl_off / ctl_len describe its
+ * payload, which is written unmasked at out[ctl_off ..), ctl_off being its
+ * absolute offset in `in`; the host answers it and submits the rest of the
+ * buffer with its next call.  A stream that has max_frames frames stops before
+ * the next frame, whatever that is.
+ * With `out` != `in`, `in` is never written, and in `out` only the bytes of
+ * returned frames' bodies and of a control payload are (within a body, the
+ * bytes behind the payload are unspecified).  With `out` == `in` masked bodies
+ * are unmasked and then decoded in place; header, key and flags bytes are
+ * never rewritten.  As for zmqg_decode_batch, a payload region holds
+ * unauthenticated plaintext until the stream reaches the end of the call.
+ * Two launches more than zmqg_decode_batch_ex with must_mask (the parse, then
+ * the unmask over every returned body), one without (two when a control
+ * payload has to be copied to an `out` that is not `in`).
+ * ZMQG_OPT_VERIFY_FIRST / _REPLAY_HOST / _STREAM_OUT are not offered. */
+typedef struct zmqg_ws_result {
+    uint64_t frames;     /* binary frames returned in the stream's slots */
+    uint64_t consumed;   /* bytes of the stream parsed (a control frame that ended the parse included) */
+    uint64_t out_bytes;  /* payload bytes of the returned frames */
+    int32_t error;       /* 0, EPROTO, EMSGSIZE */
+    int32_t ctl_opcode;  /* 0, or 8 / 9 / 10: a close / ping / pong frame ended the parse */
+    uint64_t ctl_off;    /* its payload, unmasked: out[ctl_off .. +ctl_len), absolute offset */
+    uint64_t ctl_len;
+} zmqg_ws_result;        /* 48 bytes */
+int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
+                         const uint32_t *stream_len, const uint8_t *in, int must_mask, int64_t max_msg_size,
+                         uint64_t max_frames, uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off,
+                         uint8_t *out, uint8_t *flags_out, int32_t *status_out, zmqg_ws_result *results,
+                         void *stream);
+
+/* zmqg_encode_ws_multi: zmqg_encode_zmtp_multi with ws_encoder_t's frame
+ * (src/ws_encoder.cpp:26-126) around each MESSAGE command, a msg_t without
+ * MORE / COMMAND / subscribe / cancel (src/curve_mechanism_base.cpp:166-177).
+ * zmqg_encode_zmtp_multi's contract holds -- validity, layout, fit, nonces,
+ * results, the untouched bytes, the -EINVAL cases -- with the frame format and
+ * F replaced.  `mask` is NULL for the server side (_must_mask false), else n
+ * device-accessible entries: frame i's key bytes k are BE32(mask[i]), as
+ * put_uint32 (..., random) writes them (:64-69); the device has no random
+ * source, the caller supplies what generate_random would return.  With W =
+ * zmqg_wire_size(...) and size = W + 1 the frame is: 0x82; the MASK bit (0x80
+ * with mask != NULL) ORed with the size (size <= 125), or with 126 and two
+ * bytes big endian (size <= 0xFFFF), or with 127 and eight bytes; the four key
+ * bytes when masked; the flags byte 0 ^ k[0]; the W bytes of the MESSAGE
+ * command, byte j XORed with k[(j + 1) % 4] when masked.  F(i) = 2 + (0 | 2 |
+ * 8) + (masked ? 4 : 0) + size.  results[s].out_off / out_bytes are the
+ * peer's zmqg_decode_ws_multi stream_off / stream_len.  Five launches before
+ * the encode's own (nine with device nonces), and with mask != NULL one behind
+ * it: the XOR over the bodies of the fitting frames; a frame that does not fit
+ * or is invalid stays untouched. */
+int zmqg_encode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                         const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                         const uint64_t *in_off, const uint32_t *len, const uint8_t *in, const uint32_t *mask,
+                         uint8_t *out, uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                         zmqg_zmtp_send_result *results, void *stream);
 
 /* Handshake key derivation in batches, one
  * 32-byte item per thread, items packed back to back:

@@ -28,6 +28,11 @@
 //                    results[s] (one atomic per wave and stream)
 //
 // Five launches before the encode's own, whatever n and n_streams are.
+//
+// The two kernels that know a frame's size and header, k_zsend_tiles and
+// k_zsend_frames, take the framing as a template parameter (ZsendFraming):
+// ZMTP's, or the WebSocket binary frame of zmqg_encode_ws_multi, whose masked
+// form adds one launch behind the encode (k_ws_mask_bodies, curve_ws.hpp).
 #pragma once
 
 #include <errno.h>
@@ -61,19 +66,90 @@ __device__ __forceinline__ uint32_t zsend_stream(uint32_t fs, uint32_t n_streams
     return fs;
 }
 
-// Bytes of a valid frame: the ZMTP header and the MESSAGE command
-// (k_zmtp_sizes's rule; zmqg_wire_size).
-__device__ __forceinline__ uint64_t zsend_frame_bytes(uint32_t flags, uint32_t len,
-                                                      const DevSession *__restrict__ sessions, uint32_t sid)
+// The framing around a MESSAGE command: ZMTP's (src/v2_encoder.cpp:23-60), or
+// ws_encoder_t's binary frame (src/ws_encoder.cpp:26-126) without or with a
+// masking key (zmqg_encode_ws_multi).  The layout kernels are the same for
+// all three: a framing sets a frame's bytes F and writes its header.
+enum ZsendFraming : uint32_t { kZsendZmtp = 0, kZsendWs = 1, kZsendWsMasked = 2 };
+
+// Bytes of a valid frame's MESSAGE command (zmqg_wire_size)
+__device__ __forceinline__ uint64_t zsend_wire_bytes(uint32_t flags, uint32_t len,
+                                                     const DevSession *__restrict__ sessions, uint32_t sid)
 {
     const uint32_t ct = flags & 0x1cu;
     uint64_t extra = 0;
     if (ct == 12u || ct == 16u)
         extra = sessions[sid].downgrade_sub ? 1u : (ct == 12u ? 10u : 7u);
-    const uint64_t W = 32u + 1u + extra + len;
-    return (W > 255u ? 9u : 2u) + W;
+    return 32u + 1u + extra + len;
 }
 
+// Bytes of a valid frame: the header and the MESSAGE command (ZMTP:
+// k_zmtp_sizes's rule; WebSocket: 2 bytes, the extended size of W + 1 -- the
+// flags byte counts --, the key, the flags byte).
+template <ZsendFraming FR>
+__device__ __forceinline__ uint64_t zsend_frame_bytes(uint32_t flags, uint32_t len,
+                                                      const DevSession *__restrict__ sessions, uint32_t sid)
+{
+    const uint64_t W = zsend_wire_bytes(flags, len, sessions, sid);
+    if constexpr (FR == kZsendZmtp)
+        return (W > 255u ? 9u : 2u) + W;
+    const uint64_t size = W + 1u;
+    return 2u + (size <= 125u ? 0u : size <= 0xffffu ? 2u : 8u) + (FR == kZsendWsMasked ? 4u : 0u) + size;
+}
+
+// Bytes in front of the MESSAGE command of a frame of F bytes
+template <ZsendFraming FR>
+__device__ __forceinline__ uint32_t zsend_header_bytes(uint64_t F)
+{
+    if constexpr (FR == kZsendZmtp)
+        return F > 257u ? 9u : 2u;
+    constexpr uint32_t m = FR == kZsendWsMasked ? 4u : 0u;
+    return 2u + (F <= 2u + m + 125u ? 0u : F <= 4u + m + 0xffffu ? 2u : 8u) + m + 1u;
+}
+
+// The header of a fitting frame of F bytes at h; mask: the frame's key value
+// (kZsendWsMasked), whose bytes are BE32(mask) (put_uint32, src/ws_encoder.cpp:64-69).
+template <ZsendFraming FR>
+__device__ __forceinline__ void zsend_write_header(uint8_t *h, uint64_t F, uint32_t hdr, uint32_t mask)
+{
+    const uint64_t W = F - hdr;
+    if constexpr (FR == kZsendZmtp) {
+        if (hdr == 2u) { // body <= 255 bytes: flags 0, one size byte
+            h[0] = 0;
+            h[1] = (uint8_t) W;
+        } else {
+            h[0] = kZmtpLarge;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                h[1 + k] = (uint8_t) (W >> (56 - 8 * k));
+        }
+    } else {
+        constexpr uint32_t m = FR == kZsendWsMasked ? 4u : 0u;
+        const uint64_t size = W + 1u;
+        const uint32_t ext = hdr - 3u - m;
+        h[0] = 0x82; // FIN | binary
+        h[1] = (uint8_t) ((m ? 0x80u : 0u) | (ext == 0u ? (uint32_t) size : ext == 2u ? 126u : 127u));
+        if (ext == 2u) {
+            h[2] = (uint8_t) (size >> 8);
+            h[3] = (uint8_t) size;
+        } else if (ext == 8u) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                h[2 + k] = (uint8_t) (size >> (56 - 8 * k));
+        }
+        uint8_t *q = h + 2u + ext;
+        if (m) {
+            q[0] = (uint8_t) (mask >> 24);
+            q[1] = (uint8_t) (mask >> 16);
+            q[2] = (uint8_t) (mask >> 8);
+            q[3] = (uint8_t) mask;
+            q += 4;
+        }
+        q[0] = m ? (uint8_t) (mask >> 24) : 0; // the flags byte: 0 ^ k[0]
+    }
+}
+
+template <ZsendFraming FR>
 __global__ __launch_bounds__(256) void k_zsend_tiles(uint32_t n, uint32_t T, uint32_t n_streams,
                                                     const uint32_t *__restrict__ stream_sid,
                                                     const uint32_t *__restrict__ frame_stream,
@@ -95,7 +171,7 @@ __global__ __launch_bounds__(256) void k_zsend_tiles(uint32_t n, uint32_t T, uin
         uint32_t sid;
         const uint32_t s = zsend_stream(frame_stream[i], n_streams, stream_sid, max_sessions, sid);
         if (s != kZsendNoSession)
-            atomicAdd(zsend_row + s, (unsigned long long) zsend_frame_bytes(flags[i], len[i], sessions, sid));
+            atomicAdd(zsend_row + s, (unsigned long long) zsend_frame_bytes<FR>(flags[i], len[i], sessions, sid));
     }
     __syncthreads();
     unsigned long long *row = tab + (size_t) blockIdx.x * n_streams;
@@ -224,9 +300,12 @@ __device__ __forceinline__ void zsend_group(uint32_t key, uint64_t F, uint32_t l
 // waves take their turns, in frame order, at the LDS row of running offsets.
 // Invalid lanes carry a key of their own, so they match nobody.  (The row is
 // the workgroup's whole LDS at 8,192 streams: no other shared variable.)
+// ws_key: the frames' key values (kZsendWsMasked only).
+template <ZsendFraming FR>
 __global__ __launch_bounds__(kZsendFramesThreads) void k_zsend_frames(
     uint32_t n, uint32_t T, uint32_t n_streams, const uint32_t *__restrict__ stream_sid,
     const uint32_t *__restrict__ frame_stream, const uint8_t *__restrict__ flags, const uint32_t *__restrict__ len,
+    const uint32_t *__restrict__ ws_key,
     const DevSession *__restrict__ sessions, uint32_t max_sessions, const unsigned long long *__restrict__ tab,
     const unsigned long long *__restrict__ base, uint64_t out_bytes, uint8_t *__restrict__ out,
     uint64_t *__restrict__ frame_off, int32_t *__restrict__ status_out, uint32_t *__restrict__ enc_sid,
@@ -246,7 +325,7 @@ __global__ __launch_bounds__(kZsendFramesThreads) void k_zsend_frames(
         if (i < e) {
             s = zsend_stream(frame_stream[i], n_streams, stream_sid, max_sessions, sid);
             if (s != kZsendNoSession)
-                F = zsend_frame_bytes(flags[i], len[i], sessions, sid);
+                F = zsend_frame_bytes<FR>(flags[i], len[i], sessions, sid);
         }
         const bool valid = s != kZsendNoSession;
         const uint32_t key = valid ? s : 0x80000000u | lane; // (streams are below 8,192)
@@ -275,24 +354,13 @@ __global__ __launch_bounds__(kZsendFramesThreads) void k_zsend_frames(
         const bool next_fits = __shfl((int) fit, has_next ? (int) __builtin_ctzll(higher) : (int) lane) != 0;
         if (i < e) {
             frame_off[i] = valid ? off : UINT64_MAX;
-            const uint32_t hdr = F > 257u ? 9u : 2u;
+            const uint32_t hdr = zsend_header_bytes<FR>(F);
             enc_sid[i] = fit ? sid : kZsendNoSession;
             wire_off[i] = fit ? off + hdr : 0;
             if (status_out)
                 status_out[i] = !valid ? ZMQG_ERR_SESSION : fit ? 0 : ZMQG_ERR_BOUND;
-            if (fit) {
-                uint8_t *h = out + off;
-                const uint64_t W = F - hdr;
-                if (hdr == 2u) { // body <= 255 bytes: flags 0, one size byte
-                    h[0] = 0;
-                    h[1] = (uint8_t) W;
-                } else {
-                    h[0] = kZmtpLarge;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        h[1 + k] = (uint8_t) (W >> (56 - 8 * k));
-                }
-            }
+            if (fit)
+                zsend_write_header<FR>(out + off, F, hdr, FR == kZsendWsMasked ? ws_key[i] : 0u);
         }
         if (valid) {
             zmqg_zmtp_send_result *r = results + s;

@@ -58,6 +58,7 @@
 #include "curve_zmtp.hpp"
 #include "curve_zmtp_multi.hpp"
 #include "curve_zmtp_send.hpp"
+#include "curve_ws.hpp"
 
 #ifndef ZMQG_ABLATE
 #define ZMQG_ABLATE 0
@@ -3135,11 +3136,15 @@ static uint32_t zsend_tile_frames(uint32_t nn, uint32_t keys)
     }
 }
 
-int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
-                           const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
-                           const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
-                           uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
-                           zmqg_zmtp_send_result *results, void *stream)
+// zmqg_encode_zmtp_multi and zmqg_encode_ws_multi: the layout kernels with the
+// framing FR, the encode, and -- kZsendWsMasked -- the XOR over the bodies.
+extern "C++" {
+template <ZsendFraming FR>
+static int encode_multi_impl(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                             const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                             const uint64_t *in_off, const uint32_t *len, const uint8_t *in, const uint32_t *mask,
+                             uint8_t *out, uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                             zmqg_zmtp_send_result *results, void *stream)
 {
     if (!ctx || check_n(n) || n_streams > kZsendMaxStreams || (n_streams == 0 && n > 0) || !frame_off)
         return -EINVAL;
@@ -3177,7 +3182,7 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
                        *tot = base + NS;
     const dim3 cg((NS + 255) / 256, rbs);
     if (tiles) {
-        hipLaunchKernelGGL(k_zsend_tiles, dim3(tiles), dim3(256), NS * sizeof(unsigned long long), st, nn, T, NS,
+        hipLaunchKernelGGL(k_zsend_tiles<FR>, dim3(tiles), dim3(256), NS * sizeof(unsigned long long), st, nn, T, NS,
                            stream_sid, frame_stream, flags, len, (const DevSession *) ctx->sessions,
                            ctx->max_sessions, tab, tot);
         ZCHECK(ctx, hipGetLastError());
@@ -3193,8 +3198,8 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
     hipLaunchKernelGGL(k_zsend_colscan, cg, dim3(256), 0, st, tiles, NS, tab, (const unsigned long long *) blk,
                        (const unsigned long long *) base);
     ZCHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_zsend_frames, dim3(tiles), dim3(kZsendFramesThreads), NS * sizeof(unsigned long long), st, nn,
-                       T, NS, stream_sid, frame_stream, flags, len, (const DevSession *) ctx->sessions, ctx->max_sessions,
+    hipLaunchKernelGGL(k_zsend_frames<FR>, dim3(tiles), dim3(kZsendFramesThreads), NS * sizeof(unsigned long long), st, nn,
+                       T, NS, stream_sid, frame_stream, flags, len, mask, (const DevSession *) ctx->sessions, ctx->max_sessions,
                        (const unsigned long long *) tab, (const unsigned long long *) base, out_bytes, out, frame_off,
                        status_out, z.s_sid, z.s_woff, results);
     ZCHECK(ctx, hipGetLastError());
@@ -3209,7 +3214,42 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
             return rc;
         nonce = ctx->ws.nonce;
     }
-    return zmqg_encode_batch_ex(ctx, n, z.s_sid, nonce, flags, in_off, len, in, z.s_woff, out, nullptr, stream);
+    rc = zmqg_encode_batch_ex(ctx, n, z.s_sid, nonce, flags, in_off, len, in, z.s_woff, out, nullptr, stream);
+    if (FR != kZsendWsMasked || rc)
+        return rc;
+    // the fitting frames' MESSAGE commands under their keys, in place
+    const uint64_t groups = kWsThreads / 8u, want = (n + groups - 1) / groups; // (8 lanes a frame)
+    const uint64_t cap = 8ull * (uint64_t) (ctx->cus > 0 ? ctx->cus : 256);
+    hipLaunchKernelGGL(k_ws_mask_bodies, dim3((unsigned) (want < cap ? want : cap), 4), dim3(kWsThreads), 0, st, nn,
+                       (const uint32_t *) z.s_sid, (const uint64_t *) z.s_woff, flags, len, mask,
+                       (const DevSession *) ctx->sessions, out);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+} // extern "C++"
+
+int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                           const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                           const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
+                           uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                           zmqg_zmtp_send_result *results, void *stream)
+{
+    return encode_multi_impl<kZsendZmtp>(ctx, n_streams, stream_sid, n, frame_stream, nonce, flags, in_off, len, in,
+                                         nullptr, out, out_bytes, frame_off, status_out, results, stream);
+}
+
+int zmqg_encode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                         const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                         const uint64_t *in_off, const uint32_t *len, const uint8_t *in, const uint32_t *mask,
+                         uint8_t *out, uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                         zmqg_zmtp_send_result *results, void *stream)
+{
+    if (mask)
+        return encode_multi_impl<kZsendWsMasked>(ctx, n_streams, stream_sid, n, frame_stream, nonce, flags, in_off,
+                                                 len, in, mask, out, out_bytes, frame_off, status_out, results,
+                                                 stream);
+    return encode_multi_impl<kZsendWs>(ctx, n_streams, stream_sid, n, frame_stream, nonce, flags, in_off, len, in,
+                                       nullptr, out, out_bytes, frame_off, status_out, results, stream);
 }
 
 int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint64_t in_bytes, int64_t max_msg_size,
@@ -3353,6 +3393,63 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
         o.max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
     return decode_batch_impl(ctx, slots, z.sid_fill, frame_in_off, frame_len, in, out_off, out, flags_out, status_out,
                              o.max_len ? &o : nullptr, z.fflags, nullptr, nullptr, stream);
+}
+
+int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
+                         const uint32_t *stream_len, const uint8_t *in, int must_mask, int64_t max_msg_size,
+                         uint64_t max_frames, uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off,
+                         uint8_t *out, uint8_t *flags_out, int32_t *status_out, zmqg_ws_result *results, void *stream)
+{
+    if (!ctx || !results || check_n(n_streams) || check_n(max_frames) || check_n(n_streams * max_frames))
+        return -EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    if (n_streams == 0)
+        return 0;
+    if (max_frames == 0) {
+        ZCHECK(ctx, hipMemsetAsync(results, 0, n_streams * sizeof *results, st));
+        return 0;
+    }
+    if (!stream_sid || !stream_off || !stream_len || !in || !frame_in_off || !frame_len || !out_off || !out ||
+        !flags_out || !status_out)
+        return -EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ZmtpWs &z = ctx->zw;
+    const uint64_t slots = n_streams * max_frames;
+    int rc;
+    // (the per-frame arrays are the ctx's: after the work queued on its last stream)
+    if ((rc = order_after_last(ctx, st)) || (rc = zmtp_frame_cap(ctx, slots, st)))
+        return rc;
+    // 1. the parse: one workgroup per stream, a persistent grid beyond what is
+    // resident (21 KiB of LDS a workgroup: 7 per CU); it reads `in` only
+    const uint64_t resident = 7ull * (uint64_t) (ctx->cus > 0 ? ctx->cus : 256);
+    const uint32_t g = (uint32_t) (n_streams < resident ? n_streams : resident);
+    hipLaunchKernelGGL(k_ws_streams, dim3(g), dim3(kWsThreads), 0, st, (uint32_t) n_streams, stream_sid, stream_off,
+                       stream_len, in, must_mask ? 1u : 0u, max_msg_size, max_frames, frame_in_off, frame_len, out_off,
+                       z.sid_fill, z.fflags, results);
+    ZCHECK(ctx, hipGetLastError());
+    // 2. every returned body and control payload unmasked into `out` (which
+    // may be `in`); without a key, a control payload copied to an `out` that
+    // is not `in`
+    if (must_mask) {
+        hipLaunchKernelGGL(k_ws_unmask<true>, dim3(g), dim3(kWsThreads), 0, st, (uint32_t) n_streams, max_frames, in,
+                           out, (const uint64_t *) frame_in_off, (const uint32_t *) frame_len,
+                           (const zmqg_ws_result *) results);
+        ZCHECK(ctx, hipGetLastError());
+    } else if (out != in) {
+        hipLaunchKernelGGL(k_ws_unmask<false>, dim3(g), dim3(kWsThreads), 0, st, (uint32_t) n_streams, max_frames, in,
+                           out, (const uint64_t *) frame_in_off, (const uint32_t *) frame_len,
+                           (const zmqg_ws_result *) results);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    // 3. the decode over every slot, as in zmqg_decode_zmtp_multi; masked
+    // bodies are read where the unmask put them
+    zmqg_batch_opts o{};
+    o.size = sizeof o;
+    if (max_msg_size >= 0 && (uint64_t) max_msg_size <= kMaxFrameStream)
+        o.max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
+    return decode_batch_impl(ctx, slots, z.sid_fill, frame_in_off, frame_len, must_mask ? out : in, out_off, out,
+                             flags_out, status_out, o.max_len ? &o : nullptr, z.fflags, nullptr, nullptr, stream);
 }
 
 int zmqg_decode_zmtp(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint64_t in_bytes, int64_t max_msg_size,

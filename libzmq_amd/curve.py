@@ -102,6 +102,9 @@ _lib.zmqg_decode_zmtp_async.argtypes = [_P, _U32, _P, _U64, ctypes.c_int64, _U64
 _lib.zmqg_decode_zmtp_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int64, _U64] + [_P] * 8
 _lib.zmqg_encode_zmtp_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 7 + [_U64] + [_P] * 4
 ZMTP_MULTI_TILE = 16384  # kZmtpMultiTile: bytes of a stream zmqg_decode_zmtp_multi's kernel holds in LDS at a time
+_lib.zmqg_decode_ws_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int, ctypes.c_int64, _U64] + [_P] * 8
+_lib.zmqg_encode_ws_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 8 + [_U64] + [_P] * 4
+WS_MULTI_TILE = 16384  # kWsTile: the same for zmqg_decode_ws_multi's kernel
 _lib.zmqg_scalarmult_batch.argtypes = [_P, _U64] + [_P] * 5
 _lib.zmqg_box_beforenm_batch.argtypes = [_P, _U64] + [_P] * 5
 _lib.zmqg_box_afternm_batch.argtypes = [_P, _U64] + [_P] * 8
@@ -399,6 +402,46 @@ class CurveContext:
         r = results.cpu().numpy().view(np.uint64).reshape(-1, 4)
         return [dict(frames=int(x[0]), out_off=int(x[1]), out_bytes=int(x[2]),
                      error=int(np.int32(x[3] & np.uint64(0xffffffff)))) for x in r]
+
+    def decode_ws_multi(self, stream_sid, stream_off, stream_len, inp, must_mask, max_msg_size, max_frames,
+                        frame_in_off, frame_len, out_off, out, flags_out, status_out, results, stream=None):
+        """decode_zmtp_multi for WebSocket framing (ws_decoder_t): the
+        arguments are the same, plus must_mask (True on a server's receive
+        side: every frame carries a masking key, and its body is unmasked --
+        in place when out is inp -- before it is decoded).  `results` is a
+        device int64 tensor of n_streams x 6 (one zmqg_ws_result per stream),
+        read with ws_results() once the stream is done."""
+        n = int(stream_sid.numel())
+        self._check(_lib.zmqg_decode_ws_multi(self._ctx, n, _ptr(stream_sid), _ptr(stream_off), _ptr(stream_len),
+                                              _ptr(inp), int(bool(must_mask)), max_msg_size, max_frames,
+                                              _ptr(frame_in_off), _ptr(frame_len), _ptr(out_off), _ptr(out),
+                                              _ptr(flags_out), _ptr(status_out), _ptr(results),
+                                              _stream_handle(stream)), "zmqg_decode_ws_multi")
+
+    @staticmethod
+    def ws_results(results):
+        """decode_ws_multi's `results` (synchronised) as a list of dicts, one per stream."""
+        r = results.cpu().numpy().view(np.uint64).reshape(-1, 6)
+        return [dict(frames=int(x[0]), consumed=int(x[1]), out_bytes=int(x[2]),
+                     error=int(np.int32(x[3] & np.uint64(0xffffffff))), ctl_opcode=int(np.int32(x[3] >> np.uint64(32))),
+                     ctl_off=int(x[4]), ctl_len=int(x[5])) for x in r]
+
+    def encode_ws_multi(self, stream_sid, frame_stream, nonce, flags, in_off, length, inp, mask, out, frame_off,
+                        status_out, results, stream=None, out_bytes=None):
+        """encode_zmtp_multi with WebSocket framing (ws_encoder_t's binary
+        frame around each MESSAGE command).  mask None: unmasked frames, a
+        server's send side; else an int32 tensor of n entries, the 32-bit
+        value whose big-endian bytes are frame i's masking key (what the
+        reference takes from generate_random).  `results` is read with
+        zmtp_send_results()."""
+        n_streams, n = int(stream_sid.numel()), int(frame_stream.numel())
+        if out_bytes is None:
+            out_bytes = out.numel() * out.element_size()
+        self._check(_lib.zmqg_encode_ws_multi(self._ctx, n_streams, _ptr(stream_sid), n, _ptr(frame_stream),
+                                              _ptr(nonce), _ptr(flags), _ptr(in_off), _ptr(length), _ptr(inp),
+                                              _ptr(mask), _ptr(out), int(out_bytes), _ptr(frame_off),
+                                              _ptr(status_out), _ptr(results), _stream_handle(stream)),
+                    "zmqg_encode_ws_multi")
 
     # ---- handshake key derivation (device tensors of n x 32 bytes) ----
     def scalarmult_batch(self, scalar, point, out, status_out, stream=None):
