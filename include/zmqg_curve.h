@@ -43,6 +43,9 @@
  *     src/ws_engine.cpp:887-915                      zmqg_decode_ws_multi
  *   curve_encoding_t::encode + ws_encoder_t
  *     src/ws_encoder.cpp:26-126                      zmqg_encode_ws_multi
+ *   zmq_proxy's forward over CURVE connections
+ *     src/proxy.cpp:90-138, src/fq.cpp:52-94,
+ *     src/dist.cpp:127-189, src/pipe.cpp:222-247     zmqg_forward_zmtp_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -583,6 +586,149 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
                            const uint64_t *in_off, const uint32_t *len, const uint8_t *in, uint8_t *out,
                            uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
                            zmqg_zmtp_send_result *results, void *stream);
+
+/* zmqg_forward_zmtp_multi: a broker's I/O thread in one asynchronous call --
+ * from the receive buffers of many connections to the send buffers of many
+ * connections, what zmq_proxy does message by message (src/proxy.cpp:90-138,
+ * fed by fq_t::recvpipe, src/fq.cpp:52-94, sending through lb_t or
+ * dist_t::distribute, src/dist.cpp:127-189): decrypt a frame from connection A,
+ * encrypt the same bytes for B, or for B, C and D.  It is
+ * zmqg_decode_zmtp_multi, a plan made on the device, and
+ * zmqg_encode_zmtp_multi, queued back to back: between the two the host neither
+ * synchronises, nor reads statuses back, nor uploads descriptors.
+ *
+ * Receive side.  n_streams, stream_sid, stream_off, stream_len, in,
+ * max_msg_size, max_frames, frame_in_off, frame_len, plain_off (that call's
+ * out_off), plain (its out), flags_out, status_out and results are
+ * zmqg_decode_zmtp_multi's arguments, and everything that call states holds:
+ * every output is what that call writes -- slots, results, statuses, flags,
+ * the payloads at plain[plain_off[..]], the peer nonces, plain == in, two
+ * streams on one session, stream_sid[s] >= max_sessions.
+ *
+ * Sequence.  For source stream s, Q(s) is its carried parts, entries
+ * carry_idx[s] .. carry_idx[s + 1] of carry_off / carry_len / carry_flags
+ * (payloads plain[carry_off[i] .. +carry_len[i]) with their msg_t flags,
+ * decoded by an earlier call and held back), followed by its returned frames,
+ * slots j < results[s].frames.  c(s) is its number of carried parts, d(s) =
+ * route_idx[s + 1] - route_idx[s] its number of routes, the destinations
+ * route_dst[route_idx[s] ..]; destination t sends on session dst_sid[t], and a
+ * stream that names a destination twice sends it two copies.  An element is a
+ * command when its flags carry ZMQG_MSG_COMMAND.  Commands are never forwarded
+ * and neither end nor break a message: the engine handles them itself
+ * (src/stream_engine_base.cpp:635-637) and the session keeps them out of the
+ * pipe; a carried entry with COMMAND set is skipped the same way.
+ *
+ * What is forwarded.  F(s) is the index in Q(s) of the first returned frame
+ * with a non-zero status, or |Q(s)|; E(s) the largest index below F(s) of an
+ * element that is no command and has ZMQG_MSG_MORE clear, or -1.  Exactly the
+ * non-command elements below E(s) + 1 are forwarded, each to every route of
+ * the stream: whole messages only, as parts become visible to the reader only
+ * when their message is complete (pipe_t::write, src/pipe.cpp:222-234: the
+ * ypipe is written with incomplete = more).  Messages completed before a
+ * failing frame are still delivered (stream_engine_base_t::error flushes the
+ * session, src/stream_engine_base.cpp:667-699); the incomplete tail of a failed
+ * connection is dropped (pipe_t::rollback, src/pipe.cpp:236-247).
+ * fwd[s] (n_streams entries): seq = |Q(s)|, held_first = E(s) + 1 (== seq:
+ * nothing is held), forwarded = the elements forwarded, failed = 1 when a
+ * returned frame of the stream has a non-zero status -- the host then drops
+ * what is held instead of carrying it.  Held data parts (at or behind
+ * held_first) stay decoded in `plain`: the host passes them as the stream's
+ * carry in a later call and keeps that region of `plain` alive until then (a
+ * returned frame becomes the carried part {plain_off, frame_len - 33,
+ * flags_out}).  Held commands are the host's to process now.
+ *
+ * Pairs.  Element q of stream s (q < c(s) + max_frames, carry first) and its
+ * k-th route form pair p = base(s) + q * d(s) + k, base(s) = the sum over t < s
+ * of (c(t) + max_frames) * d(t); N = base(n_streams), which the host computes
+ * from carry_idx and route_idx.  pair_off has N + 1 entries, pair_status N (or
+ * is NULL).  A pair is live when its element is forwarded.
+ *
+ * Send side.  Exactly zmqg_encode_zmtp_multi over the N pairs in pair order
+ * with n_dst streams, stream_sid = dst_sid and nonce == NULL (the sessions'
+ * device send counters).  A live pair is the frame {frame_stream = its
+ * destination, flags = the element's MORE bit alone, in = plain, in_off = the
+ * element's offset in plain, len = its payload length: frame_len - 33 of a
+ * returned frame, carry_len of a carried part}; a pair that is not live names
+ * no stream.  All of that call's rules hold, with out, out_bytes, pair_off,
+ * pair_status and dst_results as its out, out_bytes, frame_off, status_out and
+ * results: layout, fit and the prefix property, ZMQG_ERR_BOUND with no nonce
+ * taken, ENOBUFS / EINVAL in dst_results, two destinations on one session
+ * taking nonces in pair order, nothing written at or past out_bytes.  A pair
+ * that is not live, or whose destination's session is invalid, gets pair_status
+ * ZMQG_ERR_SESSION and pair_off UINT64_MAX and takes no nonce.  Each
+ * destination's run out[dst_results[t].out_off .. +out_bytes) so holds the
+ * forwarded messages in (stream, element) order: the parts of one message are
+ * contiguous and never interleaved with another source's, within a call and,
+ * through the carry, across calls.  A pair that did not fit (ZMQG_ERR_BOUND)
+ * is the host's to resend, with zmqg_encode_zmtp_multi from `plain`.
+ *
+ * Arrays marked HOST below are read on the host and copied (to pinned staging
+ * of the ctx, as zmqg_session_set_batch copies its arrays) before the call
+ * returns; a later call waits until the device has fetched them.  All others
+ * are device-accessible, and the host reads nothing back.  `out` must not
+ * overlap `in` or `plain`.
+ * Returns -EINVAL for a null ctx or args, size != sizeof(zmqg_forward_zmtp) or
+ * reserved != 0, the -EINVAL cases of the two underlying calls (n_streams,
+ * max_frames or their product above 2^31 - 1, a null results, with max_frames
+ * > 0 a null receive-side array, n_dst > 8192, max_sessions > 8192, with n_dst
+ * > 0 a null dst_sid or dst_results, a null pair_off, with N > 0 a null plain
+ * or out), a null fwd, a null route_idx, route_idx[0] != 0 or a falling
+ * route_idx, a route_dst entry >= n_dst (or a null route_dst with routes), a
+ * carry_idx that does not start at 0 or falls, null carry arrays with carried
+ * parts, N > 2^31 - 1; nothing is queued then.  With n_streams == 0 nothing is
+ * done.  With N == 0 the receive side and fwd are still done, pair_off[0] = 0
+ * and dst_results are filled as zmqg_encode_zmtp_multi fills them for n == 0.
+ * max_frames == 0 with carried parts is valid: results is zero-filled and the
+ * carries alone are flushed.
+ * Launches: zmqg_decode_zmtp_multi's (one more than zmqg_decode_batch_ex's),
+ * one copy of the HOST arrays, two for the plan (one wave per source stream;
+ * one lane per pair), then zmqg_encode_zmtp_multi's with device nonces (nine
+ * before the encode's own), whatever the sizes are.  WebSocket framing on
+ * either side and routing by content (ROUTER identities, XPUB topics) are not
+ * offered on this call. */
+typedef struct zmqg_forward_result {   /* per source stream, 32 bytes */
+    uint64_t seq;         /* elements of the stream's sequence Q(s) */
+    uint64_t held_first;  /* index in Q(s) of the first element not forwarded (== seq: none held) */
+    uint64_t forwarded;   /* elements forwarded (each to every destination of the stream) */
+    int32_t failed;       /* 1: a returned frame of the stream has a non-zero status */
+    int32_t pad;
+} zmqg_forward_result;
+typedef struct zmqg_forward_zmtp {
+    uint32_t size, reserved;                       /* sizeof(zmqg_forward_zmtp), 0 */
+    /* receive side: zmqg_decode_zmtp_multi's arguments and outputs */
+    uint64_t n_streams;
+    const uint32_t *stream_sid;
+    const uint64_t *stream_off;
+    const uint32_t *stream_len;
+    const uint8_t *in;
+    int64_t max_msg_size;
+    uint64_t max_frames;
+    uint64_t *frame_in_off;
+    uint32_t *frame_len;
+    uint64_t *plain_off;
+    uint8_t *plain;                                /* may be `in` */
+    uint8_t *flags_out;
+    int32_t *status_out;
+    zmqg_zmtp_result *results;
+    /* parts carried over from earlier calls (optional) */
+    const uint32_t *carry_idx;                     /* HOST, n_streams + 1, rising from 0; NULL = none */
+    const uint64_t *carry_off;                     /* carry_idx[n_streams] entries each: offsets into plain, */
+    const uint32_t *carry_len;                     /* payload lengths, */
+    const uint8_t *carry_flags;                    /* msg_t flags */
+    /* routes */
+    uint64_t n_dst;
+    const uint32_t *dst_sid;                       /* n_dst: the session each destination sends on */
+    const uint32_t *route_idx;                     /* HOST, n_streams + 1, rising from 0 */
+    const uint32_t *route_dst;                     /* HOST, route_idx[n_streams] entries, each < n_dst */
+    /* send side: zmqg_encode_zmtp_multi's outputs over the pairs */
+    uint8_t *out;
+    uint64_t out_bytes;
+    uint64_t *pair_off;                            /* N + 1 */
+    int32_t *pair_status;                          /* N, or NULL */
+    zmqg_zmtp_send_result *dst_results;            /* n_dst */
+    zmqg_forward_result *fwd;                      /* n_streams */
+} zmqg_forward_zmtp;
+int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream);
 
 /* WebSocket framing (ZWS 2.0 over RFC 6455): the reference's second caller of
  * the mechanism, ws_engine_t::decode_and_push (src/ws_engine.cpp:887-915),

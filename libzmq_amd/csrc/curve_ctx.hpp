@@ -88,6 +88,12 @@ struct ZmtpWs {
     DevBuf<uint32_t> s_sid;     // [s_cap] the session each frame is encoded on (or none)
     DevBuf<uint64_t> s_woff;    // [s_cap] body offsets
     DevBuf<u64ll> s_tab;        // [tiles][streams], [row blocks][streams], bases and totals [2][streams]
+    uint64_t p_cap = 0;         // zmqg_forward_zmtp_multi: pairs (the encode's inputs; not s_sid / s_woff, its own)
+    DevBuf<uint32_t> p_stream;  // [p_cap] the destination each pair goes to (or none)
+    DevBuf<uint8_t> p_flags;    // [p_cap] its MORE bit
+    DevBuf<uint64_t> p_off;     // [p_cap] its payload's offset in `plain`
+    DevBuf<uint32_t> p_len;     // [p_cap] and length
+    DevBuf<uint32_t> p_tab;     // the call's host arrays: bases, carry_idx, route_idx [3][streams + 1], route_dst
 };
 } // namespace
 
@@ -108,7 +114,8 @@ struct zmqg_ctx {
     size_t pin_bytes = 0;
     uint8_t *mpin = nullptr, *mpin_dev = nullptr; // the per-message buffer (zmqg_*_msg), device-mapped
     size_t mpin_bytes = 0;
-    // zmqg_session_set_batch: device-mapped descriptors of the last install,
+    // pinned, device-mapped staging for a call's host arrays (the descriptors
+    // of zmqg_session_set_batch's install, zmqg_forward_zmtp_multi's tables),
     // free again once `sinst_done` is reached
     uint8_t *sinst = nullptr, *sinst_dev = nullptr;
     size_t sinst_bytes = 0;

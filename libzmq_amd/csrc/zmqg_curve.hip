@@ -58,6 +58,7 @@
 #include "curve_zmtp.hpp"
 #include "curve_zmtp_multi.hpp"
 #include "curve_zmtp_send.hpp"
+#include "curve_forward.hpp"
 #include "curve_ws.hpp"
 
 #ifndef ZMQG_ABLATE
@@ -2367,6 +2368,32 @@ int zmqg_session_set(zmqg_ctx *ctx, uint32_t sid, const uint8_t precom[32], cons
     return 0;
 }
 
+// `need` bytes of the ctx's pinned staging (ctx->sinst), once the call that
+// filled it last has read it; the caller fills it, queues its reads and
+// records sinst_done behind them (under ctx->mu).
+static int sinst_room(zmqg_ctx *ctx, size_t need)
+{
+    if (ctx->sinst_done)
+        ZCHECK(ctx, hipEventSynchronize(ctx->sinst_done)); // the previous call has read its arrays
+    else
+        ZCHECK(ctx, hipEventCreateWithFlags(&ctx->sinst_done, hipEventDisableTiming));
+    if (need > ctx->sinst_bytes) {
+        if (ctx->sinst)
+            ZCHECK(ctx, hipHostFree(ctx->sinst));
+        ctx->sinst = nullptr;
+        ctx->sinst_bytes = 0;
+        hipError_t e = hipHostMalloc((void **) &ctx->sinst, need, hipHostMallocMapped | hipHostMallocPortable);
+        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
+            return -ENOMEM;
+        ZCHECK(ctx, e);
+        void *dp = nullptr;
+        ZCHECK(ctx, hipHostGetDevicePointer(&dp, ctx->sinst, 0));
+        ctx->sinst_dev = (uint8_t *) dp;
+        ctx->sinst_bytes = need;
+    }
+    return 0;
+}
+
 int zmqg_session_set_batch(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, const uint8_t *precom,
                            const uint8_t enc_prefix[16], const uint8_t dec_prefix[16], const uint8_t *downgrade,
                            const uint64_t *peer_nonce, void *stream)
@@ -2397,24 +2424,9 @@ int zmqg_session_set_batch_ex(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, co
     ZCHECK(ctx, hipSetDevice(ctx->device));
     const size_t o_peer = (4 * n + 7) & ~(size_t) 7, o_send = o_peer + 8 * n, o_down = o_send + 8 * n,
                  need = o_down + n;
-    if (ctx->sinst_done)
-        ZCHECK(ctx, hipEventSynchronize(ctx->sinst_done)); // the previous install has read its descriptors
-    else
-        ZCHECK(ctx, hipEventCreateWithFlags(&ctx->sinst_done, hipEventDisableTiming));
-    if (need > ctx->sinst_bytes) {
-        if (ctx->sinst)
-            ZCHECK(ctx, hipHostFree(ctx->sinst));
-        ctx->sinst = nullptr;
-        ctx->sinst_bytes = 0;
-        hipError_t e = hipHostMalloc((void **) &ctx->sinst, need, hipHostMallocMapped | hipHostMallocPortable);
-        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
-            return -ENOMEM;
-        ZCHECK(ctx, e);
-        void *dp = nullptr;
-        ZCHECK(ctx, hipHostGetDevicePointer(&dp, ctx->sinst, 0));
-        ctx->sinst_dev = (uint8_t *) dp;
-        ctx->sinst_bytes = need;
-    }
+    int src = sinst_room(ctx, need);
+    if (src)
+        return src;
     memcpy(ctx->sinst, sid, 4 * n);
     uint64_t *pn = (uint64_t *) (ctx->sinst + o_peer);
     for (uint64_t i = 0; i < n; ++i)
@@ -3140,6 +3152,13 @@ static uint32_t zsend_tile_frames(uint32_t nn, uint32_t keys)
 // framing FR, the encode, and -- kZsendWsMasked -- the XOR over the bodies.
 extern "C++" {
 template <ZsendFraming FR>
+static int encode_multi_locked(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                               const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                               const uint64_t *in_off, const uint32_t *len, const uint8_t *in, const uint32_t *mask,
+                               uint8_t *out, uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                               zmqg_zmtp_send_result *results, void *stream);
+
+template <ZsendFraming FR>
 static int encode_multi_impl(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
                              const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
                              const uint64_t *in_off, const uint32_t *len, const uint8_t *in, const uint32_t *mask,
@@ -3161,6 +3180,20 @@ static int encode_multi_impl(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *
         return 0;
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
+    return encode_multi_locked<FR>(ctx, n_streams, stream_sid, n, frame_stream, nonce, flags, in_off, len, in, mask,
+                                   out, out_bytes, frame_off, status_out, results, stream);
+}
+
+// The call behind its argument checks, n_streams > 0, under ctx->mu (also the
+// send side of zmqg_forward_zmtp_multi).
+template <ZsendFraming FR>
+static int encode_multi_locked(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, uint64_t n,
+                               const uint32_t *frame_stream, const uint64_t *nonce, const uint8_t *flags,
+                               const uint64_t *in_off, const uint32_t *len, const uint8_t *in, const uint32_t *mask,
+                               uint8_t *out, uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
+                               zmqg_zmtp_send_result *results, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
     ZmtpWs &z = ctx->zw;
     const uint32_t nn = (uint32_t) n, NS = (uint32_t) n_streams;
     const uint32_t T = zsend_tile_frames(nn, NS);
@@ -3351,25 +3384,15 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
                              status_out, o.max_len ? &o : nullptr, z.fflags, z.walk, result, stream);
 }
 
-int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
-                           const uint32_t *stream_len, const uint8_t *in, int64_t max_msg_size, uint64_t max_frames,
-                           uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off, uint8_t *out,
-                           uint8_t *flags_out, int32_t *status_out, zmqg_zmtp_result *results, void *stream)
+// zmqg_decode_zmtp_multi behind its argument checks, n_streams and max_frames
+// > 0, under ctx->mu (also the receive side of zmqg_forward_zmtp_multi).
+static int decode_zmtp_multi_locked(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid,
+                                    const uint64_t *stream_off, const uint32_t *stream_len, const uint8_t *in,
+                                    int64_t max_msg_size, uint64_t max_frames, uint64_t *frame_in_off,
+                                    uint32_t *frame_len, uint64_t *out_off, uint8_t *out, uint8_t *flags_out,
+                                    int32_t *status_out, zmqg_zmtp_result *results, void *stream)
 {
-    if (!ctx || !results || check_n(n_streams) || check_n(max_frames) || check_n(n_streams * max_frames))
-        return -EINVAL;
     hipStream_t st = (hipStream_t) stream;
-    ZCHECK(ctx, hipSetDevice(ctx->device));
-    if (n_streams == 0)
-        return 0;
-    if (max_frames == 0) {
-        ZCHECK(ctx, hipMemsetAsync(results, 0, n_streams * sizeof *results, st));
-        return 0;
-    }
-    if (!stream_sid || !stream_off || !stream_len || !in || !frame_in_off || !frame_len || !out_off || !out ||
-        !flags_out || !status_out)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
     ZmtpWs &z = ctx->zw;
     const uint64_t slots = n_streams * max_frames;
     int rc;
@@ -3393,6 +3416,146 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
         o.max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
     return decode_batch_impl(ctx, slots, z.sid_fill, frame_in_off, frame_len, in, out_off, out, flags_out, status_out,
                              o.max_len ? &o : nullptr, z.fflags, nullptr, nullptr, stream);
+}
+
+int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
+                           const uint32_t *stream_len, const uint8_t *in, int64_t max_msg_size, uint64_t max_frames,
+                           uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off, uint8_t *out,
+                           uint8_t *flags_out, int32_t *status_out, zmqg_zmtp_result *results, void *stream)
+{
+    if (!ctx || !results || check_n(n_streams) || check_n(max_frames) || check_n(n_streams * max_frames))
+        return -EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    if (n_streams == 0)
+        return 0;
+    if (max_frames == 0) {
+        ZCHECK(ctx, hipMemsetAsync(results, 0, n_streams * sizeof *results, st));
+        return 0;
+    }
+    if (!stream_sid || !stream_off || !stream_len || !in || !frame_in_off || !frame_len || !out_off || !out ||
+        !flags_out || !status_out)
+        return -EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return decode_zmtp_multi_locked(ctx, n_streams, stream_sid, stream_off, stream_len, in, max_msg_size, max_frames,
+                                    frame_in_off, frame_len, out_off, out, flags_out, status_out, results, stream);
+}
+
+// The receive side as zmqg_decode_zmtp_multi runs it, the plan (curve_forward.hpp)
+// and the send side as zmqg_encode_zmtp_multi runs it over the pairs, queued
+// back to back on `stream` under one hold of ctx->mu.
+int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
+{
+    if (!ctx || !args || args->size != sizeof *args || args->reserved != 0)
+        return -EINVAL;
+    const zmqg_forward_zmtp &a = *args;
+    const uint64_t S = a.n_streams, MF = a.max_frames;
+    // the two underlying calls' own cases
+    if (!a.results || check_n(S) || check_n(MF) || check_n(S * MF))
+        return -EINVAL;
+    if (a.n_dst > kZsendMaxStreams || ctx->max_sessions > kReplayMaxSessions)
+        return -EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    if (S == 0)
+        return 0;
+    if (MF > 0 && (!a.stream_sid || !a.stream_off || !a.stream_len || !a.in || !a.frame_in_off || !a.frame_len ||
+                   !a.plain_off || !a.plain || !a.flags_out || !a.status_out))
+        return -EINVAL;
+    if (!a.route_idx || a.route_idx[0] != 0 || (a.carry_idx && a.carry_idx[0] != 0) || !a.pair_off || !a.fwd)
+        return -EINVAL;
+    if (a.n_dst > 0 && (!a.dst_sid || !a.dst_results))
+        return -EINVAL;
+    // N = the pairs: every element a stream can have, times its routes
+    uint64_t N = 0;
+    for (uint64_t s = 0; s < S; ++s) {
+        if (a.route_idx[s + 1] < a.route_idx[s] || (a.carry_idx && a.carry_idx[s + 1] < a.carry_idx[s]))
+            return -EINVAL;
+        const uint64_t d = a.route_idx[s + 1] - a.route_idx[s];
+        const uint64_t q = (a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u) + MF; // (below 2^33)
+        if (d && q > 0x7fffffffull / d)
+            return -EINVAL;
+        N += q * d;
+        if (check_n(N))
+            return -EINVAL;
+    }
+    const uint32_t R = a.route_idx[S], CN = a.carry_idx ? a.carry_idx[S] : 0u;
+    if (R > 0 && !a.route_dst)
+        return -EINVAL;
+    for (uint32_t i = 0; i < R; ++i)
+        if (a.route_dst[i] >= a.n_dst)
+            return -EINVAL;
+    if (CN > 0 && (!a.carry_off || !a.carry_len || !a.carry_flags))
+        return -EINVAL;
+    if (N > 0 && (!a.plain || !a.out))
+        return -EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ZmtpWs &z = ctx->zw;
+    int rc;
+    if ((rc = order_after_last(ctx, st)))
+        return rc;
+    // the host arrays, copied before the call returns: the pinned staging, then
+    // one copy to the device, where every pair searches them
+    const size_t words = 3 * (size_t) (S + 1) + R;
+    if ((rc = sinst_room(ctx, 4 * words)))
+        return rc;
+    uint32_t *h_base = (uint32_t *) ctx->sinst, *h_cidx = h_base + (S + 1), *h_ridx = h_cidx + (S + 1),
+             *h_rdst = h_ridx + (S + 1);
+    uint32_t b = 0;
+    for (uint64_t s = 0; s <= S; ++s) {
+        h_base[s] = b;
+        h_cidx[s] = a.carry_idx ? a.carry_idx[s] : 0u;
+        h_ridx[s] = a.route_idx[s];
+        if (s < S) {
+            const uint64_t c = a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u;
+            b += (uint32_t) ((c + MF) * (a.route_idx[s + 1] - a.route_idx[s])); // (N <= 2^31 - 1, checked above)
+        }
+    }
+    if (R)
+        memcpy(h_rdst, a.route_dst, 4 * (size_t) R);
+    ZRESERVE(ctx, z.p_tab, grown_cap(z.p_tab.count, 1024, words), st);
+    ZCHECK(ctx, hipMemcpyAsync(z.p_tab, ctx->sinst, 4 * words, hipMemcpyHostToDevice, st));
+    ZCHECK(ctx, hipEventRecord(ctx->sinst_done, st));
+    if (N > z.p_cap) {
+        const uint64_t cap = grown_cap(z.p_cap, 1024, N);
+        z.p_cap = 0;
+        ZRESERVE(ctx, z.p_stream, cap, st);
+        ZRESERVE(ctx, z.p_flags, cap, st);
+        ZRESERVE(ctx, z.p_off, cap, st);
+        ZRESERVE(ctx, z.p_len, cap, st);
+        z.p_cap = cap;
+    }
+    // 1. the receive side
+    if (MF == 0)
+        ZCHECK(ctx, hipMemsetAsync(a.results, 0, S * sizeof *a.results, st));
+    else if ((rc = decode_zmtp_multi_locked(ctx, S, a.stream_sid, a.stream_off, a.stream_len, a.in, a.max_msg_size, MF,
+                                            a.frame_in_off, a.frame_len, a.plain_off, a.plain, a.flags_out,
+                                            a.status_out, a.results, stream)))
+        return rc;
+    // 2. the plan: what each stream forwards, then the encode's frame per pair
+    const uint32_t *d_base = z.p_tab, *d_cidx = d_base + (S + 1), *d_ridx = d_cidx + (S + 1),
+                   *d_rdst = d_ridx + (S + 1);
+    hipLaunchKernelGGL(k_fwd_scan, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
+                       dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, a.carry_flags,
+                       (const uint8_t *) a.flags_out, (const int32_t *) a.status_out,
+                       (const zmqg_zmtp_result *) a.results, a.fwd);
+    ZCHECK(ctx, hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(k_fwd_pairs, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
+                           (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_rdst, a.carry_off, a.carry_len, a.carry_flags,
+                           (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
+                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.p_stream.p,
+                           z.p_flags.p, z.p_off.p, z.p_len.p);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    // 3. the send side: the pairs are its frames, the destinations its streams
+    if (a.n_dst == 0) {
+        ZCHECK(ctx, hipMemsetAsync(a.pair_off, 0, sizeof(uint64_t), st));
+        return 0;
+    }
+    return encode_multi_locked<kZsendZmtp>(ctx, a.n_dst, a.dst_sid, N, z.p_stream, nullptr, z.p_flags, z.p_off,
+                                           z.p_len, a.plain, nullptr, a.out, a.out_bytes, a.pair_off, a.pair_status,
+                                           a.dst_results, stream);
 }
 
 int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,

@@ -102,6 +102,25 @@ _lib.zmqg_decode_zmtp_async.argtypes = [_P, _U32, _P, _U64, ctypes.c_int64, _U64
 _lib.zmqg_decode_zmtp_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int64, _U64] + [_P] * 8
 _lib.zmqg_encode_zmtp_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 7 + [_U64] + [_P] * 4
 ZMTP_MULTI_TILE = 16384  # kZmtpMultiTile: bytes of a stream zmqg_decode_zmtp_multi's kernel holds in LDS at a time
+
+
+class ForwardResult(ctypes.Structure):  # zmqg_forward_result
+    _fields_ = [("seq", _U64), ("held_first", _U64), ("forwarded", _U64), ("failed", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
+class ForwardZmtp(ctypes.Structure):  # zmqg_forward_zmtp
+    _fields_ = [("size", _U32), ("reserved", _U32),
+                ("n_streams", _U64), ("stream_sid", _P), ("stream_off", _P), ("stream_len", _P), ("inp", _P),
+                ("max_msg_size", ctypes.c_int64), ("max_frames", _U64), ("frame_in_off", _P), ("frame_len", _P),
+                ("plain_off", _P), ("plain", _P), ("flags_out", _P), ("status_out", _P), ("results", _P),
+                ("carry_idx", _P), ("carry_off", _P), ("carry_len", _P), ("carry_flags", _P),
+                ("n_dst", _U64), ("dst_sid", _P), ("route_idx", _P), ("route_dst", _P),
+                ("out", _P), ("out_bytes", _U64), ("pair_off", _P), ("pair_status", _P), ("dst_results", _P),
+                ("fwd", _P)]
+
+
+_lib.zmqg_forward_zmtp_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), _P]
 _lib.zmqg_decode_ws_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int, ctypes.c_int64, _U64] + [_P] * 8
 _lib.zmqg_encode_ws_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 8 + [_U64] + [_P] * 4
 WS_MULTI_TILE = 16384  # kWsTile: the same for zmqg_decode_ws_multi's kernel
@@ -402,6 +421,58 @@ class CurveContext:
         r = results.cpu().numpy().view(np.uint64).reshape(-1, 4)
         return [dict(frames=int(x[0]), out_off=int(x[1]), out_bytes=int(x[2]),
                      error=int(np.int32(x[3] & np.uint64(0xffffffff)))) for x in r]
+
+    @staticmethod
+    def forward_pair_base(route_idx, carry_idx, max_frames):
+        """base(s) of forward_zmtp_multi's pairs, n_streams + 1 entries: the
+        last one is N, the pair count (pair_off holds N + 1 entries)."""
+        r = np.asarray(route_idx, np.int64)
+        c = np.zeros_like(r) if carry_idx is None else np.asarray(carry_idx, np.int64)
+        return [0] + [int(x) for x in np.cumsum((np.diff(c) + int(max_frames)) * np.diff(r))]
+
+    def forward_zmtp_multi(self, stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                           frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx, route_dst,
+                           out, pair_off, pair_status, dst_results, fwd, carry_idx=None, carry_off=None,
+                           carry_len=None, carry_flags=None, stream=None, out_bytes=None):
+        """A broker's round in one asynchronous call (zmqg_forward_zmtp_multi):
+        decode_zmtp_multi on the first thirteen arguments (plain_off / plain
+        are its out_off / out), then every whole message of source stream s
+        re-encoded for each of its destinations route_dst[route_idx[s] ..
+        route_idx[s + 1]], destination t sending on session dst_sid[t] (int32
+        device tensor) with the device send counters, as encode_zmtp_multi
+        over the pairs: pair_off (int64, N + 1), pair_status (int32, N, or
+        None) and dst_results (int64, n_dst x 4: zmtp_send_results()) are its
+        frame_off / status_out / results, N = forward_pair_base(...)[-1].
+        route_idx, route_dst and carry_idx are host sequences, copied before
+        the call returns.  carry_idx / carry_off / carry_len / carry_flags:
+        the parts held back by earlier calls, per stream (int64 / int32 /
+        uint8 device tensors of carry_idx[-1] entries, offsets into plain).
+        fwd is a device int64 tensor of n_streams x 4 (one zmqg_forward_result
+        per stream), read with forward_results() once the stream is done."""
+        n = 0 if stream_sid is None else int(stream_sid.numel())
+        ri = np.ascontiguousarray(route_idx, dtype=np.uint32)
+        rd = np.ascontiguousarray(route_dst, dtype=np.uint32)
+        ci = None if carry_idx is None else np.ascontiguousarray(carry_idx, dtype=np.uint32)
+        if len(ri) != n + 1 or (ci is not None and len(ci) != n + 1) or len(rd) != int(ri[-1]):
+            raise ValueError("route_idx / carry_idx hold n_streams + 1 entries, route_dst route_idx[-1]")
+        if out_bytes is None:
+            out_bytes = 0 if out is None else out.numel() * out.element_size()
+        a = ForwardZmtp(ctypes.sizeof(ForwardZmtp), 0, n, _ptr(stream_sid), _ptr(stream_off), _ptr(stream_len),
+                        _ptr(inp), max_msg_size, max_frames, _ptr(frame_in_off), _ptr(frame_len), _ptr(plain_off),
+                        _ptr(plain), _ptr(flags_out), _ptr(status_out), _ptr(results),
+                        None if ci is None else ci.ctypes.data, _ptr(carry_off), _ptr(carry_len), _ptr(carry_flags),
+                        0 if dst_sid is None else int(dst_sid.numel()), _ptr(dst_sid), ri.ctypes.data,
+                        rd.ctypes.data if len(rd) else None, _ptr(out), int(out_bytes), _ptr(pair_off),
+                        _ptr(pair_status), _ptr(dst_results), _ptr(fwd))
+        self._check(_lib.zmqg_forward_zmtp_multi(self._ctx, ctypes.byref(a), _stream_handle(stream)),
+                    "zmqg_forward_zmtp_multi")
+
+    @staticmethod
+    def forward_results(fwd):
+        """forward_zmtp_multi's `fwd` (synchronised) as a list of dicts, one per source stream."""
+        r = fwd.cpu().numpy().view(np.uint64).reshape(-1, 4)
+        return [dict(seq=int(x[0]), held_first=int(x[1]), forwarded=int(x[2]),
+                     failed=int(np.int32(x[3] & np.uint64(0xffffffff)))) for x in r]
 
     def decode_ws_multi(self, stream_sid, stream_off, stream_len, inp, must_mask, max_msg_size, max_frames,
                         frame_in_off, frame_len, out_off, out, flags_out, status_out, results, stream=None):
