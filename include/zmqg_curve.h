@@ -46,6 +46,10 @@
  *   zmq_proxy's forward over CURVE connections
  *     src/proxy.cpp:90-138, src/fq.cpp:52-94,
  *     src/dist.cpp:127-189, src/pipe.cpp:222-247     zmqg_forward_zmtp_multi
+ *   xpub_t::xsend / mtrie match / dist_t::match
+ *     src/xpub.cpp:290-326,
+ *     src/generic_mtrie_impl.hpp:523-561,
+ *     src/dist.cpp:49-62                             zmqg_forward_zmtp_sub_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -684,8 +688,8 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
  * one copy of the HOST arrays, two for the plan (one wave per source stream;
  * one lane per pair), then zmqg_encode_zmtp_multi's with device nonces (nine
  * before the encode's own), whatever the sizes are.  WebSocket framing on
- * either side and routing by content (ROUTER identities, XPUB topics) are not
- * offered on this call. */
+ * either side and routing by ROUTER identities are not offered on this call;
+ * routing by XPUB topics is zmqg_forward_zmtp_sub_multi. */
 typedef struct zmqg_forward_result {   /* per source stream, 32 bytes */
     uint64_t seq;         /* elements of the stream's sequence Q(s) */
     uint64_t held_first;  /* index in Q(s) of the first element not forwarded (== seq: none held) */
@@ -729,6 +733,90 @@ typedef struct zmqg_forward_zmtp {
     zmqg_forward_result *fwd;                      /* n_streams */
 } zmqg_forward_zmtp;
 int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream);
+
+/* zmqg_forward_zmtp_sub_multi: zmqg_forward_zmtp_multi for an XSUB/XPUB proxy --
+ * every forwarded message goes only to the routes whose destination is
+ * subscribed to it, what xpub_t::xsend decides for the first part of each
+ * message (src/xpub.cpp:290-326: generic_mtrie_t::match, src/
+ * generic_mtrie_impl.hpp:523-561, marking pipes through dist_t::match, src/
+ * dist.cpp:49-62, then dist_t::send_to_matching).  The subscriptions are a flat
+ * table on the device, by destination; the decision is made there between the
+ * decode and the encode, from the plaintext the decode has left in `plain`.
+ *
+ * Base behaviour.  Everything zmqg_forward_zmtp_multi states holds -- the
+ * receive side, Q(s), F, E, fwd[s], the carry, the pair numbering and N, the
+ * send side as zmqg_encode_zmtp_multi over the pairs, fit and ENOBUFS, nonces
+ * in pair order, the -EINVAL cases -- with one change: which pairs are live.
+ * fwd[s] is unchanged: `forwarded` counts what the rule lets through, whatever
+ * matches.
+ *
+ * Messages.  The data elements of stream s are the non-command elements of Q(s)
+ * below held_first, in order.  The first one is a head, and so is every data
+ * element whose predecessor among them has ZMQG_MSG_MORE clear; commands in
+ * between change nothing.  The topic of a message is its head's whole payload:
+ * plain[carry_off .. +carry_len) of a carried head, plain[plain_off[slot] ..
+ * +frame_len[slot] - 33) of a returned frame.  A head carried from an earlier
+ * call is matched in the call that forwards its message, against that call's
+ * table (the verdict is taken when the first part is sent, and _more_send keeps
+ * it for the later parts, src/xpub.cpp:295); later parts are never looked at.
+ *
+ * Match.  Destination t's subscriptions are the prefixes j in [sub_idx[t],
+ * sub_idx[t + 1]), prefix j = sub_bytes[sub_off[j] .. +sub_len[j]).  t matches
+ * a topic when some such j has sub_len[j] <= the topic's length and its bytes
+ * equal to the topic's first sub_len[j] bytes (generic_mtrie_t::match walks the
+ * topic down the trie and reports the pipes of every node it passes).  The
+ * empty prefix matches every topic, the empty one included.  With
+ * ZMQG_SUBS_INVERT the verdict is negated (options.invert_matching,
+ * src/xpub.cpp:308-310, dist_t::reverse_match, src/dist.cpp:64-78): a
+ * destination without subscriptions then matches everything.  Two matching
+ * subscriptions of one destination give one copy (dist_t::match marks a pipe
+ * once, src/dist.cpp:51-53); a stream that routes one destination twice still
+ * gives it two.
+ *
+ * Live pairs.  Pair (element q, route k) of stream s is live when q is forwarded
+ * and destination route_dst[route_idx[s] + k] matches the topic of q's message.
+ * A pair that is not live is treated exactly as in zmqg_forward_zmtp_multi: it
+ * names no stream, gets pair_status ZMQG_ERR_SESSION and pair_off UINT64_MAX,
+ * takes no nonce and occupies no byte of `out`.  match_out[p] (N entries, or
+ * NULL) is 1 for a live pair, else 0: it tells "filtered" from "invalid
+ * session".
+ *
+ * The table.  All five arrays and match_out are device-accessible, none is a
+ * HOST array: the table lives on the device across calls, the caller updates it
+ * in stream order when a subscription changes (the SUBSCRIBE / CANCEL commands
+ * reach the host as held commands), and the call copies nothing of it.  The
+ * host cannot validate it, so the device bounds every read: sub_idx entries
+ * above n_subs are clamped to it, a falling pair of sub_idx entries is an empty
+ * range, a subscription with sub_off + sub_len > sub_bytes_len never matches
+ * and no byte of it is read; no byte outside sub_bytes[0 .. sub_bytes_len) or
+ * outside the topic is read.
+ *
+ * Returns -EINVAL for a null subs, subs->size != sizeof(zmqg_forward_subs),
+ * flag bits other than ZMQG_SUBS_INVERT, n_subs > 2^31 - 1, with n_dst > 0 a
+ * null sub_idx, with n_subs > 0 a null sub_off or sub_len, a null sub_bytes
+ * with sub_bytes_len > 0, and every case of zmqg_forward_zmtp_multi; nothing is
+ * queued then.
+ * Launches: zmqg_forward_zmtp_multi's and two more, whatever the sizes are (one
+ * wave per source stream for the heads; one wave per element for the match,
+ * the waves of heads walking their routes with a subscription a lane).  With
+ * N == 0 the two are not queued.
+ * Not offered: ROUTER identities; maintaining the table on the device from
+ * SUBSCRIBE / CANCEL commands (they stay held commands for the host);
+ * ZMQ_XPUB_MANUAL, ZMQ_XPUB_NODROP and high-water marks, the welcome message;
+ * the XSUB upstream direction; WebSocket framing. */
+#define ZMQG_SUBS_INVERT 1u            /* options.invert_matching: dist_t::reverse_match, src/dist.cpp:64-78 */
+typedef struct zmqg_forward_subs {
+    uint32_t size, flags;              /* sizeof(zmqg_forward_subs); 0 or ZMQG_SUBS_INVERT */
+    uint64_t n_subs;                   /* entries of sub_off / sub_len (<= 2^31 - 1) */
+    const uint32_t *sub_idx;           /* args->n_dst + 1: destination t owns subscriptions sub_idx[t] .. sub_idx[t+1] */
+    const uint64_t *sub_off;           /* prefix j = sub_bytes[sub_off[j] .. +sub_len[j]) */
+    const uint32_t *sub_len;
+    const uint8_t *sub_bytes;
+    uint64_t sub_bytes_len;            /* extent of sub_bytes */
+    uint8_t *match_out;                /* N entries, or NULL */
+} zmqg_forward_subs;
+int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
+                                const zmqg_forward_subs *subs, void *stream);
 
 /* WebSocket framing (ZWS 2.0 over RFC 6455): the reference's second caller of
  * the mechanism, ws_engine_t::decode_and_push (src/ws_engine.cpp:887-915),

@@ -28,6 +28,8 @@
 //
 // The host arrays of the call (the bases, carry_idx, route_idx, route_dst)
 // arrive as one table of 32-bit words: [3][n_streams + 1], then the routes.
+// zmqg_forward_zmtp_sub_multi adds a fourth row, the element bases, and two
+// kernels between the scan and the pairs (curve_fwd_match.hpp).
 #pragma once
 
 #include <stdint.h>
@@ -102,6 +104,11 @@ __global__ __launch_bounds__(kFwdThreads) void k_fwd_scan(uint32_t n_streams, ui
 // base[s] = the first pair of stream s, base[n_streams] = n.  Streams without
 // pairs share their successor's base: the pair's stream is the last one whose
 // base is not above it.
+// kSubs (zmqg_forward_zmtp_sub_multi, curve_fwd_match.hpp): a forwarded pair is
+// live only when its destination is subscribed to its message's topic, the byte
+// match[] holds at the pair index of the message's head (head[ebase[s] + q]),
+// and match_out, when asked for, says which pairs are live.
+template <bool kSubs>
 __global__ __launch_bounds__(256) void k_fwd_pairs(
     uint32_t n, uint32_t n_streams, uint64_t max_frames, const uint32_t *__restrict__ base,
     const uint32_t *__restrict__ cidx, const uint32_t *__restrict__ ridx, const uint32_t *__restrict__ rdst,
@@ -109,7 +116,8 @@ __global__ __launch_bounds__(256) void k_fwd_pairs(
     const uint8_t *__restrict__ carry_flags, const uint64_t *__restrict__ plain_off,
     const uint32_t *__restrict__ frame_len, const uint8_t *__restrict__ flags_out,
     const zmqg_forward_result *__restrict__ fwd, uint32_t *__restrict__ p_stream, uint8_t *__restrict__ p_flags,
-    uint64_t *__restrict__ p_off, uint32_t *__restrict__ p_len)
+    uint64_t *__restrict__ p_off, uint32_t *__restrict__ p_len, const uint32_t *__restrict__ ebase,
+    const uint32_t *__restrict__ head, const uint8_t *__restrict__ match, uint8_t *__restrict__ match_out)
 {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= n)
@@ -139,6 +147,12 @@ __global__ __launch_bounds__(256) void k_fwd_pairs(
         len = frame_len[j] - 33u; // (a forwarded frame has status 0: a box and a flags byte)
     }
     live = live && !(fl & ZMQG_MSG_COMMAND);
+    if (kSubs) {
+        // (head[] and match[] are written for forwarded elements and their heads only)
+        live = live && match[(uint64_t) base[s] + (uint64_t) head[ebase[s] + q] * d + k] != 0;
+        if (match_out)
+            match_out[p] = live ? 1 : 0;
+    }
     p_stream[p] = live ? rdst[r0 + k] : kZsendNoSession;
     p_flags[p] = live ? (uint8_t) (fl & ZMQG_MSG_MORE) : 0;
     p_off[p] = live ? off : 0;

@@ -59,6 +59,7 @@
 #include "curve_zmtp_multi.hpp"
 #include "curve_zmtp_send.hpp"
 #include "curve_forward.hpp"
+#include "curve_fwd_match.hpp"
 #include "curve_ws.hpp"
 
 #ifndef ZMQG_ABLATE
@@ -3444,7 +3445,12 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
 // The receive side as zmqg_decode_zmtp_multi runs it, the plan (curve_forward.hpp)
 // and the send side as zmqg_encode_zmtp_multi runs it over the pairs, queued
 // back to back on `stream` under one hold of ctx->mu.
-int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
+// With `subs` (zmqg_forward_zmtp_sub_multi, its table checked by the caller) the
+// plan also finds every element's head and matches each head's topic against
+// its routes' subscriptions (curve_fwd_match.hpp): two launches more, and a
+// fourth row in the table.  Without it, zmqg_forward_zmtp_multi's launches.
+static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
+                              void *stream)
 {
     if (!ctx || !args || args->size != sizeof *args || args->reserved != 0)
         return -EINVAL;
@@ -3496,21 +3502,28 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
         return rc;
     // the host arrays, copied before the call returns: the pinned staging, then
     // one copy to the device, where every pair searches them
-    const size_t words = 3 * (size_t) (S + 1) + R;
+    // (with subs a fourth row: ebase, each routed stream's first element among
+    // the elements of the routed streams -- at most N of them)
+    const size_t rows = subs ? 4 : 3, words = rows * (size_t) (S + 1) + R;
     if ((rc = sinst_room(ctx, 4 * words)))
         return rc;
     uint32_t *h_base = (uint32_t *) ctx->sinst, *h_cidx = h_base + (S + 1), *h_ridx = h_cidx + (S + 1),
-             *h_rdst = h_ridx + (S + 1);
-    uint32_t b = 0;
+             *h_ebase = h_ridx + (S + 1), *h_rdst = h_base + rows * (S + 1);
+    uint32_t b = 0, eb = 0;
     for (uint64_t s = 0; s <= S; ++s) {
         h_base[s] = b;
         h_cidx[s] = a.carry_idx ? a.carry_idx[s] : 0u;
         h_ridx[s] = a.route_idx[s];
+        if (subs)
+            h_ebase[s] = eb;
         if (s < S) {
             const uint64_t c = a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u;
             b += (uint32_t) ((c + MF) * (a.route_idx[s + 1] - a.route_idx[s])); // (N <= 2^31 - 1, checked above)
+            if (a.route_idx[s + 1] != a.route_idx[s])
+                eb += (uint32_t) (c + MF);
         }
     }
+    const uint64_t EN = eb;
     if (R)
         memcpy(h_rdst, a.route_dst, 4 * (size_t) R);
     ZRESERVE(ctx, z.p_tab, grown_cap(z.p_tab.count, 1024, words), st);
@@ -3525,6 +3538,18 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
         ZRESERVE(ctx, z.p_len, cap, st);
         z.p_cap = cap;
     }
+    if (subs && N > z.m_cap) {
+        const uint64_t cap = grown_cap(z.m_cap, 1024, N);
+        z.m_cap = 0;
+        ZRESERVE(ctx, z.p_match, cap, st);
+        z.m_cap = cap;
+    }
+    if (subs && EN > z.e_cap) {
+        const uint64_t cap = grown_cap(z.e_cap, 1024, EN);
+        z.e_cap = 0;
+        ZRESERVE(ctx, z.e_head, cap, st);
+        z.e_cap = cap;
+    }
     // 1. the receive side
     if (MF == 0)
         ZCHECK(ctx, hipMemsetAsync(a.results, 0, S * sizeof *a.results, st));
@@ -3534,18 +3559,42 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
         return rc;
     // 2. the plan: what each stream forwards, then the encode's frame per pair
     const uint32_t *d_base = z.p_tab, *d_cidx = d_base + (S + 1), *d_ridx = d_cidx + (S + 1),
-                   *d_rdst = d_ridx + (S + 1);
+                   *d_ebase = d_ridx + (S + 1), *d_rdst = d_base + rows * (S + 1);
     hipLaunchKernelGGL(k_fwd_scan, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
                        dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, a.carry_flags,
                        (const uint8_t *) a.flags_out, (const int32_t *) a.status_out,
                        (const zmqg_zmtp_result *) a.results, a.fwd);
     ZCHECK(ctx, hipGetLastError());
-    if (N > 0) {
-        hipLaunchKernelGGL(k_fwd_pairs, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
+    if (N > 0 && subs) {
+        // the heads (one wave per source stream), then each head's topic against
+        // its routes' subscriptions (one wave per element; N > 0: EN > 0)
+        hipLaunchKernelGGL(k_fwd_heads, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
+                           dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
+                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p);
+        ZCHECK(ctx, hipGetLastError());
+        const uint64_t per = kFwdMatchThreads / 64u;
+        hipLaunchKernelGGL(k_fwd_match, dim3((unsigned) ((EN + per - 1) / per)), dim3(kFwdMatchThreads), 0, st,
+                           (uint32_t) EN, (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_ebase, d_rdst, a.carry_off,
+                           a.carry_len, (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
+                           (const uint8_t *) a.plain, (const zmqg_forward_result *) a.fwd,
+                           (const uint32_t *) z.e_head.p, (uint32_t) subs->n_subs, subs->sub_idx, subs->sub_off,
+                           subs->sub_len, subs->sub_bytes, subs->sub_bytes_len, subs->flags & ZMQG_SUBS_INVERT,
+                           z.p_match.p);
+        ZCHECK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_fwd_pairs<true>, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
                            (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_rdst, a.carry_off, a.carry_len, a.carry_flags,
                            (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
                            (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.p_stream.p,
-                           z.p_flags.p, z.p_off.p, z.p_len.p);
+                           z.p_flags.p, z.p_off.p, z.p_len.p, d_ebase, (const uint32_t *) z.e_head.p,
+                           (const uint8_t *) z.p_match.p, subs->match_out);
+        ZCHECK(ctx, hipGetLastError());
+    } else if (N > 0) {
+        hipLaunchKernelGGL(k_fwd_pairs<false>, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
+                           (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_rdst, a.carry_off, a.carry_len, a.carry_flags,
+                           (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
+                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.p_stream.p,
+                           z.p_flags.p, z.p_off.p, z.p_len.p, (const uint32_t *) nullptr, (const uint32_t *) nullptr,
+                           (const uint8_t *) nullptr, (uint8_t *) nullptr);
         ZCHECK(ctx, hipGetLastError());
     }
     // 3. the send side: the pairs are its frames, the destinations its streams
@@ -3556,6 +3605,24 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
     return encode_multi_locked<kZsendZmtp>(ctx, a.n_dst, a.dst_sid, N, z.p_stream, nullptr, z.p_flags, z.p_off,
                                            z.p_len, a.plain, nullptr, a.out, a.out_bytes, a.pair_off, a.pair_status,
                                            a.dst_results, stream);
+}
+
+int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
+{
+    return forward_multi_impl(ctx, args, nullptr, stream);
+}
+
+// The table's launch-free checks; what the host cannot see (sub_idx's entries,
+// the subscriptions' extents) the match kernel bounds itself.
+int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
+                                void *stream)
+{
+    if (!ctx || !args || !subs || subs->size != sizeof *subs || (subs->flags & ~ZMQG_SUBS_INVERT) != 0)
+        return -EINVAL;
+    if (check_n(subs->n_subs) || (args->n_dst > 0 && !subs->sub_idx) ||
+        (subs->n_subs > 0 && (!subs->sub_off || !subs->sub_len)) || (subs->sub_bytes_len > 0 && !subs->sub_bytes))
+        return -EINVAL;
+    return forward_multi_impl(ctx, args, subs, stream);
 }
 
 int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,

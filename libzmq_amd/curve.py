@@ -120,7 +120,16 @@ class ForwardZmtp(ctypes.Structure):  # zmqg_forward_zmtp
                 ("fwd", _P)]
 
 
+SUBS_INVERT = 1  # ZMQG_SUBS_INVERT
+
+
+class ForwardSubs(ctypes.Structure):  # zmqg_forward_subs
+    _fields_ = [("size", _U32), ("flags", _U32), ("n_subs", _U64), ("sub_idx", _P), ("sub_off", _P),
+                ("sub_len", _P), ("sub_bytes", _P), ("sub_bytes_len", _U64), ("match_out", _P)]
+
+
 _lib.zmqg_forward_zmtp_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), _P]
+_lib.zmqg_forward_zmtp_sub_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardSubs), _P]
 _lib.zmqg_decode_ws_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int, ctypes.c_int64, _U64] + [_P] * 8
 _lib.zmqg_encode_ws_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 8 + [_U64] + [_P] * 4
 WS_MULTI_TILE = 16384  # kWsTile: the same for zmqg_decode_ws_multi's kernel
@@ -449,6 +458,19 @@ class CurveContext:
         uint8 device tensors of carry_idx[-1] entries, offsets into plain).
         fwd is a device int64 tensor of n_streams x 4 (one zmqg_forward_result
         per stream), read with forward_results() once the stream is done."""
+        a, keep = self._forward_args(stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                                     frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
+                                     route_dst, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
+                                     carry_len, carry_flags, out_bytes)
+        self._check(_lib.zmqg_forward_zmtp_multi(self._ctx, ctypes.byref(a), _stream_handle(stream)),
+                    "zmqg_forward_zmtp_multi")
+        del keep
+
+    @staticmethod
+    def _forward_args(stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off, frame_len,
+                      plain_off, plain, flags_out, status_out, results, dst_sid, route_idx, route_dst, out, pair_off,
+                      pair_status, dst_results, fwd, carry_idx, carry_off, carry_len, carry_flags, out_bytes):
+        """The zmqg_forward_zmtp of a forward call, and the host arrays it points into."""
         n = 0 if stream_sid is None else int(stream_sid.numel())
         ri = np.ascontiguousarray(route_idx, dtype=np.uint32)
         rd = np.ascontiguousarray(route_dst, dtype=np.uint32)
@@ -464,8 +486,48 @@ class CurveContext:
                         0 if dst_sid is None else int(dst_sid.numel()), _ptr(dst_sid), ri.ctypes.data,
                         rd.ctypes.data if len(rd) else None, _ptr(out), int(out_bytes), _ptr(pair_off),
                         _ptr(pair_status), _ptr(dst_results), _ptr(fwd))
-        self._check(_lib.zmqg_forward_zmtp_multi(self._ctx, ctypes.byref(a), _stream_handle(stream)),
-                    "zmqg_forward_zmtp_multi")
+        return a, (ri, rd, ci)
+
+    def forward_zmtp_sub_multi(self, stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                               frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
+                               route_dst, out, pair_off, pair_status, dst_results, fwd, sub_idx, sub_off, sub_len,
+                               sub_bytes, n_subs=None, sub_bytes_len=None, invert=False, match_out=None,
+                               carry_idx=None, carry_off=None, carry_len=None, carry_flags=None, stream=None,
+                               out_bytes=None):
+        """forward_zmtp_multi for an XPUB side (zmqg_forward_zmtp_sub_multi): a
+        forwarded message goes only to the routes whose destination holds a
+        subscription that is a prefix of the message's first part.  The table
+        is device tensors, CSR by destination (forward_subs_table() builds the
+        arrays): sub_idx int32 of n_dst + 1, sub_off int64 and sub_len int32
+        of n_subs (default: sub_off's length), sub_bytes uint8 of
+        sub_bytes_len (default: its length).  invert: ZMQG_SUBS_INVERT.
+        match_out: a device uint8 tensor of N entries, 1 for a live pair, or
+        None.  The table is read on the stream and not copied."""
+        a, keep = self._forward_args(stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                                     frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
+                                     route_dst, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
+                                     carry_len, carry_flags, out_bytes)
+        if n_subs is None:
+            n_subs = 0 if sub_off is None else int(sub_off.numel())
+        if sub_bytes_len is None:
+            sub_bytes_len = 0 if sub_bytes is None else int(sub_bytes.numel())
+        sb = ForwardSubs(ctypes.sizeof(ForwardSubs), SUBS_INVERT if invert else 0, int(n_subs), _ptr(sub_idx),
+                         _ptr(sub_off), _ptr(sub_len), _ptr(sub_bytes), int(sub_bytes_len), _ptr(match_out))
+        self._check(_lib.zmqg_forward_zmtp_sub_multi(self._ctx, ctypes.byref(a), ctypes.byref(sb),
+                                                     _stream_handle(stream)), "zmqg_forward_zmtp_sub_multi")
+        del keep
+
+    @staticmethod
+    def forward_subs_table(prefixes_per_dst):
+        """The subscription table of forward_zmtp_sub_multi for a list (by
+        destination) of lists of bytes: (sub_idx uint32 of n_dst + 1, sub_off
+        uint64, sub_len uint32, sub_bytes uint8) as numpy arrays, the
+        prefixes packed back to back in order."""
+        flat = [bytes(p) for d in prefixes_per_dst for p in d]
+        idx = np.cumsum([0] + [len(d) for d in prefixes_per_dst]).astype(np.uint32)
+        lens = np.array([len(p) for p in flat], np.uint32)
+        off = (np.cumsum(lens, dtype=np.uint64) - lens).astype(np.uint64)
+        return idx, off, lens, np.frombuffer(b"".join(flat), np.uint8).copy()
 
     @staticmethod
     def forward_results(fwd):
