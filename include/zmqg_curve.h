@@ -50,6 +50,9 @@
  *     src/xpub.cpp:290-326,
  *     src/generic_mtrie_impl.hpp:523-561,
  *     src/dist.cpp:49-62                             zmqg_forward_zmtp_sub_multi
+ *   router_t::xrecv / xsend, lookup_out_pipe
+ *     src/router.cpp:263-332, :161-261,
+ *     src/socket_base.cpp:2187-2200                  zmqg_forward_zmtp_router_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -688,8 +691,9 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
  * one copy of the HOST arrays, two for the plan (one wave per source stream;
  * one lane per pair), then zmqg_encode_zmtp_multi's with device nonces (nine
  * before the encode's own), whatever the sizes are.  WebSocket framing on
- * either side and routing by ROUTER identities are not offered on this call;
- * routing by XPUB topics is zmqg_forward_zmtp_sub_multi. */
+ * either side is not offered on this call; routing by XPUB topics is
+ * zmqg_forward_zmtp_sub_multi, routing by ROUTER identities
+ * zmqg_forward_zmtp_router_multi. */
 typedef struct zmqg_forward_result {   /* per source stream, 32 bytes */
     uint64_t seq;         /* elements of the stream's sequence Q(s) */
     uint64_t held_first;  /* index in Q(s) of the first element not forwarded (== seq: none held) */
@@ -800,7 +804,8 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
  * wave per source stream for the heads; one wave per element for the match,
  * the waves of heads walking their routes with a subscription a lane).  With
  * N == 0 the two are not queued.
- * Not offered: ROUTER identities; maintaining the table on the device from
+ * Not offered: ROUTER identities (zmqg_forward_zmtp_router_multi, which does not
+ * combine with this table); maintaining the table on the device from
  * SUBSCRIBE / CANCEL commands (they stay held commands for the host);
  * ZMQ_XPUB_MANUAL, ZMQ_XPUB_NODROP and high-water marks, the welcome message;
  * the XSUB upstream direction; WebSocket framing. */
@@ -817,6 +822,126 @@ typedef struct zmqg_forward_subs {
 } zmqg_forward_subs;
 int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
                                 const zmqg_forward_subs *subs, void *stream);
+
+/* zmqg_forward_zmtp_router_multi: zmqg_forward_zmtp_multi for a proxy with a
+ * ROUTER side -- a request/reply broker, a worker pool.  What a ROUTER does to
+ * messages is decided per message from the plaintext the decode has left in
+ * `plain`:
+ *   ZMQG_ROUTER_PREPEND  the receive side is a ROUTER (router_t::xrecv,
+ *     src/router.cpp:263-332): every message gets the sending peer's routing id
+ *     in front, as an extra first part with MORE set.
+ *   ZMQG_ROUTER_ROUTE    the send side is a ROUTER (router_t::xsend,
+ *     src/router.cpp:161-261): the first part of every message is an address; an
+ *     address without MORE is a malformed message and is silently ignored
+ *     (:168-171, :207-211); otherwise it is looked up among the peers' routing
+ *     ids (lookup_out_pipe, src/socket_base.cpp:2187-2200: an exact match on the
+ *     blob_t), it is never sent itself, and the remaining parts go to that peer,
+ *     or are dropped when there is none (:221, :251-254, ZMQ_ROUTER_MANDATORY
+ *     off).
+ * flags == 0 is valid and is exactly zmqg_forward_zmtp_multi (no other field of
+ * `router` is read, dest_out is not written).  `args` is that call's struct.
+ *
+ * Base behaviour.  Everything zmqg_forward_zmtp_multi states holds -- the
+ * receive side, Q(s), F, E, fwd[s] (unchanged: `forwarded` counts what the rule
+ * lets through), the carry, the send side as zmqg_encode_zmtp_multi over the
+ * pairs, fit and ENOBUFS, nonces in pair order, the -EINVAL cases -- with two
+ * changes: the pair space, and which pairs are live.  Data elements, heads and
+ * messages are defined as in zmqg_forward_zmtp_sub_multi; every message below
+ * held_first is complete.
+ *
+ * Outgoing message.  A message's data parts; with PREPEND the part {flags MORE,
+ * payload id(s)} in front of them, id(s) = plain[src_id_off[s] ..
+ * +src_id_len[s]): the source ids live in `plain`, where the encode reads every
+ * other payload, in a region the host owns (with plain == in the gaps between
+ * streams will do: nothing outside a stream is parsed).  src_id_off / src_id_len
+ * are trusted as carry_off / carry_len are.
+ * Without ROUTE every part of the outgoing message goes to every route of its
+ * stream.  With ROUTE route_idx and route_dst are not read and may be NULL, and
+ * every stream has one route slot: the address is the first part of the outgoing
+ * message -- the head's payload, or id(s) with PREPEND also set (a ROUTER to
+ * ROUTER proxy).  An address part with MORE clear (possible only without
+ * PREPEND) makes the message malformed: it is dropped.  Otherwise the
+ * destination t is the lookup of the address bytes; the remaining parts go to
+ * t, or are dropped when the lookup finds nothing; the address part is never
+ * sent.  A head carried from an earlier call is looked up in the call that
+ * forwards its message, in that call's table.
+ *
+ * Lookup.  Defined for any table, since the host cannot validate one on the
+ * device.  Entry j, id_bytes[id_off[j] .. +id_len[j]), is void when id_off[j] >
+ * id_bytes_len or id_len[j] > id_bytes_len - id_off[j]: none of its bytes is
+ * read, it orders as the empty id and never equals an address.  less(a, b) is
+ * blob_t::operator< (src/blob.hpp:92): memcmp over the shorter length gives < 0,
+ * or gives 0 and a is shorter.  Start with lo = 0, hi = n_ids; while lo < hi,
+ * mid = lo + (hi - lo) / 2, and less(entry[mid], address) ? lo = mid + 1 : hi =
+ * mid.  The address is found when lo < n_ids, entry[lo] is not void and has the
+ * address's length and bytes, and id_dst[lo] < n_dst.  On a table sorted by less
+ * with distinct ids that is std::map::find's answer; two ids may name one
+ * destination.  No byte outside id_bytes[0 .. id_bytes_len) and no byte outside
+ * the address is read.  The table lives on the device across calls (none of its
+ * arrays is a HOST array, the call copies nothing of it); the caller updates it
+ * in stream order when a peer connects or leaves.
+ *
+ * Pair space.  m = 2 with PREPEND set and ROUTE clear, else 1; d'(s) = 1 with
+ * ROUTE, else d(s).  Stream s, slot and route k form pair p = base(s) + slot *
+ * d'(s) + k, base(s) = the sum over t < s of m * (c(t) + max_frames) * d'(t).
+ * With m = 1 slot q is element q; with m = 2 slot 2q + 1 is element q and slot
+ * 2q the id part in front of it.  N = base(n_streams) <= 2^31 - 1; pair_off has
+ * N + 1 entries, pair_status and dest_out N.
+ *
+ * Live pairs.  An id slot is live when its element is a forwarded head: the
+ * frame {MORE, in_off = src_id_off[s], len = src_id_len[s]} to route k, with a
+ * nonce like any frame.  Without ROUTE an element slot is live when its element
+ * is forwarded.  With ROUTE it is live when the element is forwarded, is not the
+ * address part, its message is not malformed and the lookup of its message's
+ * address was found; its destination is the one found.  A pair that is not live
+ * is zmqg_forward_zmtp_multi's: no stream, pair_status ZMQG_ERR_SESSION,
+ * pair_off UINT64_MAX, no nonce, no byte of `out`.
+ * dest_out[p] (device-accessible, N entries, or NULL): a live pair's destination
+ * index (also when that destination's session is invalid and the encode reports
+ * ZMQG_ERR_SESSION); ZMQG_ROUTE_ADDRESS for a forwarded head consumed as an
+ * address, ZMQG_ROUTE_MALFORMED for the head of a one-part message,
+ * ZMQG_ROUTE_UNKNOWN for a forwarded non-address part whose lookup failed (what
+ * a host that wants ZMQ_ROUTER_MANDATORY-style reporting reads),
+ * ZMQG_ROUTE_NONE for everything else.  With ROUTE and PREPEND together there
+ * is no slot for the address and no ADDRESS entry.
+ *
+ * Returns -EINVAL for a null router, size != sizeof(zmqg_forward_router), flag
+ * bits other than the two; with PREPEND and n_streams > 0 a null src_id_off or
+ * src_id_len; with ROUTE n_ids > 2^31 - 1, with n_ids > 0 a null id_off, id_len
+ * or id_dst, a null id_bytes with id_bytes_len > 0; and every case of
+ * zmqg_forward_zmtp_multi, the route_idx / route_dst cases skipped under ROUTE
+ * and N computed as above (under ROUTE also N > 0 with n_dst == 0, the send
+ * side's own case of frames without streams, which routes cannot reach);
+ * nothing is queued then.
+ * Launches: with PREPEND alone zmqg_forward_zmtp_multi's and one more (the
+ * heads, one wave per source stream); with ROUTE two more (the heads; one wave
+ * per element for the lookup, the waves of heads searching the table with the
+ * lanes over the bytes of each compare).  With N == 0 the extra ones are not
+ * queued.
+ * Not offered: ZMQ_ROUTER_MANDATORY and its errors, ZMQ_ROUTER_HANDOVER,
+ * ZMQ_ROUTER_RAW; maintaining the id table on the device; DEALER's round-robin
+ * choice (lb_t), which the host makes through route_dst; high-water marks;
+ * WebSocket framing; combining with the subscription table. */
+#define ZMQG_ROUTER_PREPEND 1u   /* receive side is a ROUTER: router_t::xrecv */
+#define ZMQG_ROUTER_ROUTE   2u   /* send side is a ROUTER: router_t::xsend */
+#define ZMQG_ROUTE_NONE      0xffffffffu  /* slot not forwarded (held, command, past seq, unused id slot) */
+#define ZMQG_ROUTE_ADDRESS   0xfffffffeu  /* the address part: consumed, never sent */
+#define ZMQG_ROUTE_UNKNOWN   0xfffffffdu  /* part of a message whose address names no destination: dropped */
+#define ZMQG_ROUTE_MALFORMED 0xfffffffcu  /* a one-part message on a ROUTE call: dropped */
+typedef struct zmqg_forward_router {
+    uint32_t size, flags;        /* sizeof(zmqg_forward_router); PREPEND | ROUTE (0 = zmqg_forward_zmtp_multi) */
+    const uint64_t *src_id_off;  /* PREPEND: n_streams; stream s's id = plain[src_id_off[s] .. +src_id_len[s]) */
+    const uint32_t *src_id_len;  /* PREPEND: n_streams (any length, 0 included) */
+    uint64_t n_ids;              /* ROUTE: entries of the id table (<= 2^31 - 1) */
+    const uint64_t *id_off;      /* id j = id_bytes[id_off[j] .. +id_len[j]) */
+    const uint32_t *id_len;
+    const uint32_t *id_dst;      /* the destination (index into dst_sid) id j names */
+    const uint8_t *id_bytes;
+    uint64_t id_bytes_len;       /* extent of id_bytes */
+    uint32_t *dest_out;          /* N entries, or NULL */
+} zmqg_forward_router;
+int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
+                                   const zmqg_forward_router *router, void *stream);
 
 /* WebSocket framing (ZWS 2.0 over RFC 6455): the reference's second caller of
  * the mechanism, ws_engine_t::decode_and_push (src/ws_engine.cpp:887-915),

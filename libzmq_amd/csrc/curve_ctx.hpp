@@ -94,11 +94,13 @@ struct ZmtpWs {
     DevBuf<uint64_t> p_off;     // [p_cap] its payload's offset in `plain`
     DevBuf<uint32_t> p_len;     // [p_cap] and length
     DevBuf<uint32_t> p_tab;     // the call's host arrays: bases, carry_idx, route_idx [3][streams + 1], route_dst
-                                // (zmqg_forward_zmtp_sub_multi: [4], the element bases behind route_idx)
+                                // (zmqg_forward_zmtp_sub_multi / _router_multi: [4], the element bases behind route_idx)
     uint64_t m_cap = 0;         // zmqg_forward_zmtp_sub_multi: pairs
     DevBuf<uint8_t> p_match;    // [m_cap] at a head's pairs: its route's destination is subscribed to the topic
     uint64_t e_cap = 0;         // and elements of the routed streams
     DevBuf<uint32_t> e_head;    // [e_cap] the index in Q(s) of each forwarded element's head
+    uint64_t v_cap = 0;         // zmqg_forward_zmtp_router_multi with ROUTE: elements
+    DevBuf<uint32_t> e_verdict; // [v_cap] at a head: the destination its address names, or UNKNOWN / MALFORMED
 };
 } // namespace
 

@@ -30,6 +30,8 @@
 // arrive as one table of 32-bit words: [3][n_streams + 1], then the routes.
 // zmqg_forward_zmtp_sub_multi adds a fourth row, the element bases, and two
 // kernels between the scan and the pairs (curve_fwd_match.hpp).
+// zmqg_forward_zmtp_router_multi has the same fourth row, the heads, a lookup
+// of every head's address and a pairs kernel of its own (curve_fwd_route.hpp).
 #pragma once
 
 #include <stdint.h>

@@ -60,6 +60,7 @@
 #include "curve_zmtp_send.hpp"
 #include "curve_forward.hpp"
 #include "curve_fwd_match.hpp"
+#include "curve_fwd_route.hpp"
 #include "curve_ws.hpp"
 
 #ifndef ZMQG_ABLATE
@@ -3449,9 +3450,19 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
 // plan also finds every element's head and matches each head's topic against
 // its routes' subscriptions (curve_fwd_match.hpp): two launches more, and a
 // fourth row in the table.  Without it, zmqg_forward_zmtp_multi's launches.
+// With `rt` (zmqg_forward_zmtp_router_multi with a flag set, its own fields
+// checked by the caller; never together with subs) the pairs are the router pair
+// space (curve_fwd_route.hpp): the heads, with ROUTE the lookup of every head's
+// address, and the router's own pairs kernel in place of k_fwd_pairs.
 static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
-                              void *stream)
+                              const zmqg_forward_router *rt, void *stream)
 {
+    static_assert(kFwdRouteNone == ZMQG_ROUTE_NONE && kFwdRouteAddress == ZMQG_ROUTE_ADDRESS &&
+                      kFwdRouteUnknown == ZMQG_ROUTE_UNKNOWN && kFwdRouteMalformed == ZMQG_ROUTE_MALFORMED &&
+                      kFwdRouterPrepend == ZMQG_ROUTER_PREPEND && kFwdRouterRoute == ZMQG_ROUTER_ROUTE,
+                  "curve_fwd_route.hpp restates the header's values");
+    const bool route = rt && (rt->flags & ZMQG_ROUTER_ROUTE), prepend = rt && (rt->flags & ZMQG_ROUTER_PREPEND);
+    const uint64_t slots_m = prepend && !route ? 2u : 1u; // m: an id slot in front of every element
     if (!ctx || !args || args->size != sizeof *args || args->reserved != 0)
         return -EINVAL;
     const zmqg_forward_zmtp &a = *args;
@@ -3468,24 +3479,25 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
     if (MF > 0 && (!a.stream_sid || !a.stream_off || !a.stream_len || !a.in || !a.frame_in_off || !a.frame_len ||
                    !a.plain_off || !a.plain || !a.flags_out || !a.status_out))
         return -EINVAL;
-    if (!a.route_idx || a.route_idx[0] != 0 || (a.carry_idx && a.carry_idx[0] != 0) || !a.pair_off || !a.fwd)
+    if ((!route && (!a.route_idx || a.route_idx[0] != 0)) || (a.carry_idx && a.carry_idx[0] != 0) || !a.pair_off ||
+        !a.fwd)
         return -EINVAL;
     if (a.n_dst > 0 && (!a.dst_sid || !a.dst_results))
         return -EINVAL;
     // N = the pairs: every element a stream can have, times its routes
     uint64_t N = 0;
     for (uint64_t s = 0; s < S; ++s) {
-        if (a.route_idx[s + 1] < a.route_idx[s] || (a.carry_idx && a.carry_idx[s + 1] < a.carry_idx[s]))
+        if ((!route && a.route_idx[s + 1] < a.route_idx[s]) || (a.carry_idx && a.carry_idx[s + 1] < a.carry_idx[s]))
             return -EINVAL;
-        const uint64_t d = a.route_idx[s + 1] - a.route_idx[s];
-        const uint64_t q = (a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u) + MF; // (below 2^33)
+        const uint64_t d = route ? 1u : a.route_idx[s + 1] - a.route_idx[s];
+        const uint64_t q = slots_m * ((a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u) + MF); // (below 2^34)
         if (d && q > 0x7fffffffull / d)
             return -EINVAL;
         N += q * d;
         if (check_n(N))
             return -EINVAL;
     }
-    const uint32_t R = a.route_idx[S], CN = a.carry_idx ? a.carry_idx[S] : 0u;
+    const uint32_t R = route ? 0u : a.route_idx[S], CN = a.carry_idx ? a.carry_idx[S] : 0u;
     if (R > 0 && !a.route_dst)
         return -EINVAL;
     for (uint32_t i = 0; i < R; ++i)
@@ -3494,6 +3506,8 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
     if (CN > 0 && (!a.carry_off || !a.carry_len || !a.carry_flags))
         return -EINVAL;
     if (N > 0 && (!a.plain || !a.out))
+        return -EINVAL;
+    if (route && N > 0 && a.n_dst == 0) // (the send side's own case: frames and no streams; routes cannot name none)
         return -EINVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
     ZmtpWs &z = ctx->zw;
@@ -3504,7 +3518,7 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
     // one copy to the device, where every pair searches them
     // (with subs a fourth row: ebase, each routed stream's first element among
     // the elements of the routed streams -- at most N of them)
-    const size_t rows = subs ? 4 : 3, words = rows * (size_t) (S + 1) + R;
+    const size_t rows = subs || rt ? 4 : 3, words = rows * (size_t) (S + 1) + R;
     if ((rc = sinst_room(ctx, 4 * words)))
         return rc;
     uint32_t *h_base = (uint32_t *) ctx->sinst, *h_cidx = h_base + (S + 1), *h_ridx = h_cidx + (S + 1),
@@ -3513,13 +3527,14 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
     for (uint64_t s = 0; s <= S; ++s) {
         h_base[s] = b;
         h_cidx[s] = a.carry_idx ? a.carry_idx[s] : 0u;
-        h_ridx[s] = a.route_idx[s];
-        if (subs)
+        h_ridx[s] = route ? (uint32_t) s : a.route_idx[s]; // (ROUTE: d'(s) = 1)
+        if (rows == 4)
             h_ebase[s] = eb;
         if (s < S) {
             const uint64_t c = a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u;
-            b += (uint32_t) ((c + MF) * (a.route_idx[s + 1] - a.route_idx[s])); // (N <= 2^31 - 1, checked above)
-            if (a.route_idx[s + 1] != a.route_idx[s])
+            const uint32_t ds = route ? 1u : a.route_idx[s + 1] - a.route_idx[s];
+            b += (uint32_t) (slots_m * (c + MF) * ds); // (N <= 2^31 - 1, checked above)
+            if (ds)
                 eb += (uint32_t) (c + MF);
         }
     }
@@ -3544,11 +3559,17 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
         ZRESERVE(ctx, z.p_match, cap, st);
         z.m_cap = cap;
     }
-    if (subs && EN > z.e_cap) {
+    if ((subs || rt) && EN > z.e_cap) {
         const uint64_t cap = grown_cap(z.e_cap, 1024, EN);
         z.e_cap = 0;
         ZRESERVE(ctx, z.e_head, cap, st);
         z.e_cap = cap;
+    }
+    if (route && EN > z.v_cap) {
+        const uint64_t cap = grown_cap(z.v_cap, 1024, EN);
+        z.v_cap = 0;
+        ZRESERVE(ctx, z.e_verdict, cap, st);
+        z.v_cap = cap;
     }
     // 1. the receive side
     if (MF == 0)
@@ -3588,6 +3609,32 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
                            z.p_flags.p, z.p_off.p, z.p_len.p, d_ebase, (const uint32_t *) z.e_head.p,
                            (const uint8_t *) z.p_match.p, subs->match_out);
         ZCHECK(ctx, hipGetLastError());
+    } else if (N > 0 && rt) {
+        // the heads; with ROUTE the lookup of every head's address (one wave per
+        // element; N > 0: EN > 0); the router pair space
+        hipLaunchKernelGGL(k_fwd_heads, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
+                           dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
+                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p);
+        ZCHECK(ctx, hipGetLastError());
+        if (route) {
+            const uint64_t per = kFwdRouteThreads / 64u;
+            hipLaunchKernelGGL(k_fwd_route, dim3((unsigned) ((EN + per - 1) / per)), dim3(kFwdRouteThreads), 0, st,
+                               (uint32_t) EN, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_off, a.carry_len,
+                               a.carry_flags, (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
+                               (const uint8_t *) a.flags_out, (const uint8_t *) a.plain,
+                               (const zmqg_forward_result *) a.fwd, (const uint32_t *) z.e_head.p,
+                               (uint32_t) prepend, rt->src_id_off, rt->src_id_len, rt->n_ids, rt->id_off, rt->id_len,
+                               rt->id_dst, rt->id_bytes, rt->id_bytes_len, a.n_dst, z.e_verdict.p);
+            ZCHECK(ctx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_fwd_pairs_router, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
+                           (uint32_t) S, MF, rt->flags, d_base, d_cidx, d_ridx, d_rdst, d_ebase, a.carry_off,
+                           a.carry_len, a.carry_flags, (const uint64_t *) a.plain_off,
+                           (const uint32_t *) a.frame_len, (const uint8_t *) a.flags_out,
+                           (const zmqg_forward_result *) a.fwd, (const uint32_t *) z.e_head.p,
+                           (const uint32_t *) z.e_verdict.p, rt->src_id_off, rt->src_id_len, z.p_stream.p,
+                           z.p_flags.p, z.p_off.p, z.p_len.p, rt->dest_out);
+        ZCHECK(ctx, hipGetLastError());
     } else if (N > 0) {
         hipLaunchKernelGGL(k_fwd_pairs<false>, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
                            (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_rdst, a.carry_off, a.carry_len, a.carry_flags,
@@ -3609,7 +3656,7 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
 
 int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
 {
-    return forward_multi_impl(ctx, args, nullptr, stream);
+    return forward_multi_impl(ctx, args, nullptr, nullptr, stream);
 }
 
 // The table's launch-free checks; what the host cannot see (sub_idx's entries,
@@ -3622,7 +3669,24 @@ int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, co
     if (check_n(subs->n_subs) || (args->n_dst > 0 && !subs->sub_idx) ||
         (subs->n_subs > 0 && (!subs->sub_off || !subs->sub_len)) || (subs->sub_bytes_len > 0 && !subs->sub_bytes))
         return -EINVAL;
-    return forward_multi_impl(ctx, args, subs, stream);
+    return forward_multi_impl(ctx, args, subs, nullptr, stream);
+}
+
+// The router struct's launch-free checks; the id table's contents the lookup
+// bounds itself (curve_fwd_route.hpp).  flags == 0 is zmqg_forward_zmtp_multi.
+int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_router *router,
+                                   void *stream)
+{
+    if (!ctx || !args || !router || router->size != sizeof *router ||
+        (router->flags & ~(ZMQG_ROUTER_PREPEND | ZMQG_ROUTER_ROUTE)) != 0)
+        return -EINVAL;
+    if ((router->flags & ZMQG_ROUTER_PREPEND) && args->n_streams > 0 && (!router->src_id_off || !router->src_id_len))
+        return -EINVAL;
+    if ((router->flags & ZMQG_ROUTER_ROUTE) &&
+        (check_n(router->n_ids) || (router->n_ids > 0 && (!router->id_off || !router->id_len || !router->id_dst)) ||
+         (router->id_bytes_len > 0 && !router->id_bytes)))
+        return -EINVAL;
+    return forward_multi_impl(ctx, args, nullptr, router->flags ? router : nullptr, stream);
 }
 
 int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,

@@ -128,7 +128,18 @@ class ForwardSubs(ctypes.Structure):  # zmqg_forward_subs
                 ("sub_len", _P), ("sub_bytes", _P), ("sub_bytes_len", _U64), ("match_out", _P)]
 
 
+ROUTER_PREPEND, ROUTER_ROUTE = 1, 2  # ZMQG_ROUTER_*
+ROUTE_NONE, ROUTE_ADDRESS, ROUTE_UNKNOWN, ROUTE_MALFORMED = 0xffffffff, 0xfffffffe, 0xfffffffd, 0xfffffffc  # ZMQG_ROUTE_*
+
+
+class ForwardRouter(ctypes.Structure):  # zmqg_forward_router
+    _fields_ = [("size", _U32), ("flags", _U32), ("src_id_off", _P), ("src_id_len", _P), ("n_ids", _U64),
+                ("id_off", _P), ("id_len", _P), ("id_dst", _P), ("id_bytes", _P), ("id_bytes_len", _U64),
+                ("dest_out", _P)]
+
+
 _lib.zmqg_forward_zmtp_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), _P]
+_lib.zmqg_forward_zmtp_router_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardRouter), _P]
 _lib.zmqg_forward_zmtp_sub_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardSubs), _P]
 _lib.zmqg_decode_ws_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int, ctypes.c_int64, _U64] + [_P] * 8
 _lib.zmqg_encode_ws_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 8 + [_U64] + [_P] * 4
@@ -472,10 +483,13 @@ class CurveContext:
                       pair_status, dst_results, fwd, carry_idx, carry_off, carry_len, carry_flags, out_bytes):
         """The zmqg_forward_zmtp of a forward call, and the host arrays it points into."""
         n = 0 if stream_sid is None else int(stream_sid.numel())
-        ri = np.ascontiguousarray(route_idx, dtype=np.uint32)
-        rd = np.ascontiguousarray(route_dst, dtype=np.uint32)
         ci = None if carry_idx is None else np.ascontiguousarray(carry_idx, dtype=np.uint32)
-        if len(ri) != n + 1 or (ci is not None and len(ci) != n + 1) or len(rd) != int(ri[-1]):
+        if route_idx is None:  # (forward_zmtp_router_multi with ROUTER_ROUTE: no routes are read)
+            ri, rd = None, np.zeros(0, np.uint32)
+        else:
+            ri = np.ascontiguousarray(route_idx, dtype=np.uint32)
+            rd = np.ascontiguousarray(route_dst, dtype=np.uint32)
+        if (ri is not None and (len(ri) != n + 1 or len(rd) != int(ri[-1]))) or (ci is not None and len(ci) != n + 1):
             raise ValueError("route_idx / carry_idx hold n_streams + 1 entries, route_dst route_idx[-1]")
         if out_bytes is None:
             out_bytes = 0 if out is None else out.numel() * out.element_size()
@@ -483,7 +497,8 @@ class CurveContext:
                         _ptr(inp), max_msg_size, max_frames, _ptr(frame_in_off), _ptr(frame_len), _ptr(plain_off),
                         _ptr(plain), _ptr(flags_out), _ptr(status_out), _ptr(results),
                         None if ci is None else ci.ctypes.data, _ptr(carry_off), _ptr(carry_len), _ptr(carry_flags),
-                        0 if dst_sid is None else int(dst_sid.numel()), _ptr(dst_sid), ri.ctypes.data,
+                        0 if dst_sid is None else int(dst_sid.numel()), _ptr(dst_sid),
+                        None if ri is None else ri.ctypes.data,
                         rd.ctypes.data if len(rd) else None, _ptr(out), int(out_bytes), _ptr(pair_off),
                         _ptr(pair_status), _ptr(dst_results), _ptr(fwd))
         return a, (ri, rd, ci)
@@ -528,6 +543,65 @@ class CurveContext:
         lens = np.array([len(p) for p in flat], np.uint32)
         off = (np.cumsum(lens, dtype=np.uint64) - lens).astype(np.uint64)
         return idx, off, lens, np.frombuffer(b"".join(flat), np.uint8).copy()
+
+    @staticmethod
+    def forward_router_pair_base(flags, route_idx, carry_idx, max_frames):
+        """base(s) of forward_zmtp_router_multi's pairs, n_streams + 1 entries,
+        the last one N: stream s owns m * (c(s) + max_frames) * d'(s) pairs, m
+        = 2 with ROUTER_PREPEND alone (an id slot in front of every element),
+        d' = 1 with ROUTER_ROUTE (route_idx is not read then; n_streams is
+        taken from carry_idx, or route_idx when carry_idx is None)."""
+        route = bool(flags & ROUTER_ROUTE)
+        m = 2 if flags & ROUTER_PREPEND and not route else 1
+        n = len(carry_idx if carry_idx is not None else route_idx) - 1
+        d = np.ones(n, np.int64) if route else np.diff(np.asarray(route_idx, np.int64))
+        c = np.zeros(n, np.int64) if carry_idx is None else np.diff(np.asarray(carry_idx, np.int64))
+        return [0] + [int(x) for x in np.cumsum(m * (c + int(max_frames)) * d)]
+
+    @staticmethod
+    def forward_router_table(ids_with_dst):
+        """The id table of forward_zmtp_router_multi for (id bytes,
+        destination) pairs: sorted as blob_t orders (bytes compare that way in
+        Python), (id_off uint64, id_len uint32, id_dst uint32, id_bytes uint8)
+        as numpy arrays, the ids packed back to back in order."""
+        rows = sorted((bytes(i), int(d)) for i, d in ids_with_dst)
+        lens = np.array([len(i) for i, _ in rows], np.uint32)
+        off = (np.cumsum(lens, dtype=np.uint64) - lens).astype(np.uint64)
+        return (off, lens, np.array([d for _, d in rows], np.uint32),
+                np.frombuffer(b"".join(i for i, _ in rows), np.uint8).copy())
+
+    def forward_zmtp_router_multi(self, stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames,
+                                  frame_in_off, frame_len, plain_off, plain, flags_out, status_out, results, dst_sid,
+                                  route_idx, route_dst, out, pair_off, pair_status, dst_results, fwd, flags,
+                                  src_id_off=None, src_id_len=None, id_off=None, id_len=None, id_dst=None,
+                                  id_bytes=None, n_ids=None, id_bytes_len=None, dest_out=None, carry_idx=None,
+                                  carry_off=None, carry_len=None, carry_flags=None, stream=None, out_bytes=None):
+        """forward_zmtp_multi for a proxy with a ROUTER side
+        (zmqg_forward_zmtp_router_multi).  flags: ROUTER_PREPEND (every
+        message gets its source's routing id in front: src_id_off int64 and
+        src_id_len int32 device tensors of n_streams, offsets into plain),
+        ROUTER_ROUTE (the first part of every message is an address, looked up
+        in the id table and consumed: id_off int64, id_len int32, id_dst int32
+        of n_ids (default: id_off's length), id_bytes uint8 of id_bytes_len
+        (default: its length), device tensors that forward_router_table()
+        builds; route_idx / route_dst may be None), both, or 0 (the parent
+        call).  dest_out: a device int32 tensor of N entries
+        (forward_router_pair_base(...)[-1]) that receives each pair's
+        destination or ROUTE_NONE / _ADDRESS / _UNKNOWN / _MALFORMED, or None.
+        The table is read on the stream and not copied."""
+        a, keep = self._forward_args(stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                                     frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
+                                     route_dst, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
+                                     carry_len, carry_flags, out_bytes)
+        if n_ids is None:
+            n_ids = 0 if id_off is None else int(id_off.numel())
+        if id_bytes_len is None:
+            id_bytes_len = 0 if id_bytes is None else int(id_bytes.numel())
+        rt = ForwardRouter(ctypes.sizeof(ForwardRouter), int(flags), _ptr(src_id_off), _ptr(src_id_len), int(n_ids),
+                           _ptr(id_off), _ptr(id_len), _ptr(id_dst), _ptr(id_bytes), int(id_bytes_len), _ptr(dest_out))
+        self._check(_lib.zmqg_forward_zmtp_router_multi(self._ctx, ctypes.byref(a), ctypes.byref(rt),
+                                                        _stream_handle(stream)), "zmqg_forward_zmtp_router_multi")
+        del keep
 
     @staticmethod
     def forward_results(fwd):
