@@ -297,7 +297,8 @@ __device__ __forceinline__ void poly_absorb64(fe &h, const fe &r, const uint32_t
 // and lets 2^130 = 5/4 fold into s_k = r_k + r_k/4.  19 v_mad_u64_u32 and one
 // v_mul_lo_u32 per 16-byte block, against 25 v_mad_u64_u32 plus the limb
 // split of the radix-2^26 form (measured 0.72x the Poly1305 time of that
-// form in the frame loop, tools/frames_proto.hip).
+// form in the frame loop, tools/frames_proto.hip); carries and the next
+// block's words move by up to eight more v_mad_u64_u32 (poly32_mul_add).
 struct Poly32 {
     uint32_t h0, h1, h2, h3, h4;
 };
@@ -319,37 +320,103 @@ __device__ __forceinline__ PolyKey32 poly32_key(uint32_t k0, uint32_t k1, uint32
     return k;
 }
 
-// h = (h + m + hib * 2^128) * r, partially reduced (h4 <= 4 on return).
-// Carries are 32-bit add-with-carry chains (v_add_co / v_addc_co); written
-// as 64-bit sums the compiler materialises zero high halves and 64-bit adds
-// (245 instructions per window against 165 this way).
+// The constant 1 in a scalar register the compiler cannot see through: a
+// v_mad_u64_u32 by it adds a 32-bit word to a 64-bit sum in one instruction
+// that neither reads nor leaves a carry (written as a 64-bit add it becomes
+// v_add_co + v_addc_co, two links of a carry chain).  Two of them, which the
+// compiler cannot tell are equal: x * one + y * one it rewrites as
+// (x + y) * one, a 64-bit add and two multiplies.
+__device__ __forceinline__ uint32_t poly32_one()
+{
+    uint32_t one;
+    asm("s_mov_b32 %0, 1" : "=s"(one));
+    return one;
+}
+
+__device__ __forceinline__ uint32_t poly32_uno()
+{
+    uint32_t uno;
+    asm("s_movk_i32 %0, 1" : "=s"(uno));
+    return uno;
+}
+
+// a * r (+ n + nhib * 2^128 when NEXT: the next block, added on the way) for
+// a = h + m already summed, partially reduced.  No carry chain: a wave alone
+// on its SIMD pays gfx950's two wait states between a VALU that writes a
+// carry and the VALU that reads it as an s_nop, and a chain has nothing
+// independent to put there, so the word carries travel in the high halves of
+// 64-bit sums instead.
+//   in:   a0..a3 < 2^32, a4 <= 8;  r0 < 2^28, r1..r3 < 2^28 multiples of 4,
+//         s_k = 5 r_k / 4 < 5 * 2^26;  n0..n3 < 2^32, nhib <= 1
+//   d0 = a0 r0 + a1 s3 + a2 s2 + a3 s1            < 19 * 2^58
+//   d1 = a0 r1 + a1 r0 + a2 s3 + a3 s2 + a4 s1    < 18 * 2^58 + 5 * 2^29
+//   d2 = a0 r2 + a1 r1 + a2 r0 + a3 s3 + a4 s2    < 17 * 2^58 + 5 * 2^29
+//   d3 = a0 r3 + a1 r2 + a2 r1 + a3 r0 + a4 s3    < 16 * 2^58 + 5 * 2^29: d3 >> 32 <= 2^30
+//   a r = d0 + d1 2^32 + d2 2^64 + (d3 mod 2^32) 2^96 + g 2^128 (mod p) with
+//   g  = a4 r0 + (d3 >> 32)                       < 2^31 + 2^30 + 1
+// The part of g at and above 2^130 folds into d0 before any carry moves
+// (2^130 = 5): d0 += 5 (g >> 2) < 19 * 2^58 + 2^32, and g & 3 stays at 2^128.
+//   e0 = d0 + n0                                  < 19 * 2^58 + 2^33
+//   t1 = d1 + (e0 >> 32) + n1,  t2 = d2 + (t1 >> 32) + n2                  < 2^63
+//   t3 = d3 + (t2 >> 32) + n3: (t3 >> 32) - (d3 >> 32) <= 2 is the carry out of word 3
+//   out = (e0, t1, t2, t3 mod 2^32;  (g & 3) + that carry + nhib <= 6;  <= 4 without NEXT)
+template <bool NEXT>
+__device__ __forceinline__ Poly32 poly32_mul_add(const Poly32 &a, const PolyKey32 &k, uint32_t n0, uint32_t n1,
+                                                 uint32_t n2, uint32_t n3, uint32_t nhib)
+{
+    const uint32_t one = poly32_one(), uno = poly32_uno();
+    uint64_t d0 = mad64(a.h3, k.s1, mad64(a.h2, k.s2, mad64(a.h1, k.s3, (uint64_t) a.h0 * k.r0)));
+    const uint64_t d1 =
+        mad64(a.h4, k.s1, mad64(a.h3, k.s2, mad64(a.h2, k.s3, mad64(a.h1, k.r0, (uint64_t) a.h0 * k.r1))));
+    const uint64_t d2 =
+        mad64(a.h4, k.s2, mad64(a.h3, k.s3, mad64(a.h2, k.r0, mad64(a.h1, k.r1, (uint64_t) a.h0 * k.r2))));
+    const uint64_t d3 =
+        mad64(a.h4, k.s3, mad64(a.h3, k.r0, mad64(a.h2, k.r1, mad64(a.h1, k.r2, (uint64_t) a.h0 * k.r3))));
+    const uint32_t d3h = (uint32_t) (d3 >> 32);
+    const uint32_t g = a.h4 * k.r0 + d3h;
+    d0 = mad64(g >> 2, 5u, d0);
+    const uint32_t w = (g & 3u) - d3h; // (mod 2^32: t3's high half brings d3h back)
+    if (NEXT)
+        d0 = mad64(n0, uno, d0);
+    uint64_t t1 = mad64((uint32_t) (d0 >> 32), one, d1);
+    if (NEXT)
+        t1 = mad64(n1, uno, t1);
+    uint64_t t2 = mad64((uint32_t) (t1 >> 32), one, d2);
+    if (NEXT)
+        t2 = mad64(n2, uno, t2);
+    uint64_t t3 = mad64((uint32_t) (t2 >> 32), one, d3);
+    if (NEXT)
+        t3 = mad64(n3, uno, t3);
+    Poly32 o;
+    o.h0 = (uint32_t) d0;
+    o.h1 = (uint32_t) t1;
+    o.h2 = (uint32_t) t2;
+    o.h3 = (uint32_t) t3;
+    o.h4 = (uint32_t) (t3 >> 32) + w + (NEXT ? nhib : 0u);
+    return o;
+}
+
+// h + m + hib * 2^128 for h4 <= 6: the one carry chain a run of blocks
+// keeps (its first block's); the fifth word comes to at most 8.
+__device__ __forceinline__ Poly32 poly32_add(const Poly32 &h, uint32_t m0, uint32_t m1, uint32_t m2, uint32_t m3,
+                                             uint32_t hib)
+{
+    unsigned c;
+    Poly32 a;
+    a.h0 = __builtin_addc(h.h0, m0, 0u, &c);
+    a.h1 = __builtin_addc(h.h1, m1, c, &c);
+    a.h2 = __builtin_addc(h.h2, m2, c, &c);
+    a.h3 = __builtin_addc(h.h3, m3, c, &c);
+    a.h4 = h.h4 + hib + c;
+    return a;
+}
+
+// h = (h + m + hib * 2^128) * r, partially reduced (h4 <= 6 on entry, <= 4
+// on return).
 __device__ __forceinline__ void poly32_block(Poly32 &h, uint32_t m0, uint32_t m1, uint32_t m2, uint32_t m3,
                                              uint32_t hib, const PolyKey32 &k)
 {
-    unsigned c;
-    const uint32_t a0 = __builtin_addc(h.h0, m0, 0u, &c);
-    const uint32_t a1 = __builtin_addc(h.h1, m1, c, &c);
-    const uint32_t a2 = __builtin_addc(h.h2, m2, c, &c);
-    const uint32_t a3 = __builtin_addc(h.h3, m3, c, &c);
-    const uint32_t a4 = h.h4 + hib + c;
-    const uint64_t d0 = mad64(a3, k.s1, mad64(a2, k.s2, mad64(a1, k.s3, (uint64_t) a0 * k.r0)));
-    const uint64_t d1 = mad64(a4, k.s1, mad64(a3, k.s2, mad64(a2, k.s3, mad64(a1, k.r0, (uint64_t) a0 * k.r1))));
-    const uint64_t d2 = mad64(a4, k.s2, mad64(a3, k.s3, mad64(a2, k.r0, mad64(a1, k.r1, (uint64_t) a0 * k.r2))));
-    const uint64_t d3 = mad64(a4, k.s3, mad64(a3, k.r0, mad64(a2, k.r1, mad64(a1, k.r2, (uint64_t) a0 * k.r3))));
-    // h = d0 + d1 2^32 + d2 2^64 + d3 2^96 + (a4 r0) 2^128
-    const uint32_t h0 = (uint32_t) d0;
-    const uint32_t h1 = __builtin_addc((uint32_t) d1, (uint32_t) (d0 >> 32), 0u, &c);
-    const uint32_t c1 = (uint32_t) (d1 >> 32) + c;
-    const uint32_t h2 = __builtin_addc((uint32_t) d2, c1, 0u, &c);
-    const uint32_t c2 = (uint32_t) (d2 >> 32) + c;
-    const uint32_t h3 = __builtin_addc((uint32_t) d3, c2, 0u, &c);
-    const uint32_t h4 = a4 * k.r0 + (uint32_t) (d3 >> 32) + c;
-    const uint32_t f = (h4 >> 2) + (h4 & ~3u); // 5 * (h >> 130)
-    h.h0 = __builtin_addc(h0, f, 0u, &c);
-    h.h1 = __builtin_addc(h1, 0u, c, &c);
-    h.h2 = __builtin_addc(h2, 0u, c, &c);
-    h.h3 = __builtin_addc(h3, 0u, c, &c);
-    h.h4 = (h4 & 3u) + c;
+    h = poly32_mul_add<false>(poly32_add(h, m0, m1, m2, m3, hib), k, 0u, 0u, 0u, 0u, 0u);
 }
 
 // Absorb the ciphertext blocks of one 64-byte keystream window: the window's
@@ -380,12 +447,22 @@ __device__ __forceinline__ void poly32_window(Poly32 &h, const PolyKey32 &k, con
     }
 }
 
-// The four full blocks of an interior window.
-__device__ __forceinline__ void poly32_window_full(Poly32 &h, const PolyKey32 &k, const uint32_t c[16])
+// The four full blocks of an interior window, or (from2, wave-uniform) the
+// two of a whole window 0 in slots 2 and 3: each block but the last adds the
+// next one on its way out (poly32_mul_add), so the run has one carry chain.
+__device__ __forceinline__ void poly32_window_full(Poly32 &h, const PolyKey32 &k, const uint32_t c[16],
+                                                   bool from2 = false)
 {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        poly32_block(h, c[4 * j], c[4 * j + 1], c[4 * j + 2], c[4 * j + 3], 1u, k);
+    Poly32 a;
+    if (from2) {
+        a = poly32_add(h, c[8], c[9], c[10], c[11], 1u);
+    } else {
+        a = poly32_add(h, c[0], c[1], c[2], c[3], 1u);
+        a = poly32_mul_add<true>(a, k, c[4], c[5], c[6], c[7], 1u);
+        a = poly32_mul_add<true>(a, k, c[8], c[9], c[10], c[11], 1u);
+    }
+    a = poly32_mul_add<true>(a, k, c[12], c[13], c[14], c[15], 1u);
+    h = poly32_mul_add<false>(a, k, 0u, 0u, 0u, 0u, 0u);
 }
 
 // Conversions between the two forms (the chunked path's Horner runs in radix

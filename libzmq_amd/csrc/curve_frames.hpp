@@ -1385,8 +1385,10 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     // Uniform steps.  While window t + 1 lies wholly inside every one of the
     // wave's 64 streams (t + 2 < the wave's smallest window count; a lane
     // without a frame has none), each lane is active, off its tail and its
-    // last window, its previous window was four full blocks, and a granule of
-    // window t + 1 is moved exactly where it is moved at all (sq_lim != 0).
+    // last window, its previous window was four full blocks (step 1: window
+    // 0's two, in block slots 2 and 3 -- a whole first window on every lane,
+    // as uniform as the four), and a granule of window t + 1 is moved exactly
+    // where it is moved at all (sq_lim != 0).
     // Such a step takes its lane predicates as constants and its five DMA
     // predicates as exec masks made once, here.
     const uint32_t min_nw = __builtin_amdgcn_readfirstlane(~wave_max_u32(~nw));
@@ -1643,7 +1645,9 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             if (ZMQG_FRAMES_ABLATE & 64)
                 hf.h0 ^= cp[0] ^ cp[5] ^ cp[11];
             else
-                poly32_window_full(hf, pk, cp);
+                // (window 0 holds two blocks; the compiler keeps t in a vector
+                // register, and a branch on it would issue both sides)
+                poly32_window_full(hf, pk, cp, UNI && __builtin_amdgcn_readfirstlane(t) == 1u);
             h.h0 = full ? hf.h0 : h.h0;
             h.h1 = full ? hf.h1 : h.h1;
             h.h2 = full ? hf.h2 : h.h2;
@@ -1789,7 +1793,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     if (steps > 1u) {
 #pragma unroll 1
         for (uint32_t t = 1; t < steps; ++t) {
-            if (ZMQG_SEQ_UNI && t >= 2u && t + 2u < min_nw)
+            if (ZMQG_SEQ_UNI && t + 2u < min_nw)
                 step(std::true_type{}, t);
             else
                 step(std::false_type{}, t);
