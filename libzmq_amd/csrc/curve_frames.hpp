@@ -37,46 +37,6 @@
 // neighbouring frames are never touched.
 #pragma once
 
-#ifndef ZMQG_FRAMES_ABLATE
-#define ZMQG_FRAMES_ABLATE 0 // timing/counting experiments only: k_frames: 1 no Poly1305, 2 no stores, 4 no input shift; k_frames_seq: 8 no stores, 16 no loads, 32 no Salsa20, 64 no Poly1305, 128 stores to 64-byte-aligned places (whole lines); k_frames_lds: 512 no partial edge granules, 1024 the encode head as two aligned dwordx4
-#endif
-
-
-#ifndef ZMQG_SEQ_STORE
-#define ZMQG_SEQ_STORE 0 // k_frames_seq window stores: 0 default policy, 3 sc0 sc1 (experiments)
-#endif
-
-// one output dwordx4 of a window (the seq kernel's per-lane stores)
-__device__ __forceinline__ void seq_store4(uint64_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w)
-{
-    typedef unsigned int v4_ __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(1))) v4_ __attribute__((aligned(4))) G4_;
-    if (ZMQG_SEQ_STORE == 3)
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(a), "v"((v4_){x, y, z, w}) : "memory");
-    else
-        *(G4_ *) (uintptr_t) a = (v4_){x, y, z, w};
-}
-
-#ifndef ZMQG_SEQ_COOPST
-#define ZMQG_SEQ_COOPST 2 // k_frames_seq under ZMQG_OPT_STREAM_OUT (decode: 64-byte-aligned payloads): each step's chunks stored by the wave cooperatively (16 frames x 64 B per instruction) through LDS, a step later (2); 0: each lane its own always
-#endif
-#ifndef ZMQG_SEQ_SKIP5
-#define ZMQG_SEQ_SKIP5 1 // LDS-DMA input: no fifth granule for 16-byte-aligned frames (k_frames_seq, k_frames_lds)
-#endif
-#ifndef ZMQG_SEQ_LBREC
-#define ZMQG_SEQ_LBREC 1 // k_frames_seq decode, ordered grids of at most kFramesBS workgroups: the one-round look-back over self-validating records, each wave alone (0: lookback_excl, for timing)
-#endif
-#ifndef ZMQG_SEQ_UNI
-#define ZMQG_SEQ_UNI 1 // k_frames_seq: the specialised step for a wave whose 64 frames are all inside their streams (0: the general step always, for timing)
-#endif
-#ifndef ZMQG_SEQ_AL64
-#define ZMQG_SEQ_AL64 1 // k_frames_seq decode: 64-byte payload chunks when every payload of a wave starts 64-byte aligned (0: off, for timing)
-#endif
-
-#ifndef ZMQG_FR_BS
-#define ZMQG_FR_BS 256 // frame-kernel workgroup size (threads)
-#endif
-
 #include "../../include/zmqg_curve.h"
 #include "curve_device.hpp"
 #include "curve_lbrec.hpp"
@@ -84,7 +44,16 @@ __device__ __forceinline__ void seq_store4(uint64_t a, uint32_t x, uint32_t y, u
 
 namespace zmqg {
 
-constexpr uint32_t kFramesBS = ZMQG_FR_BS, kFramesWaves = kFramesBS / 64;
+constexpr uint32_t kFramesBS = 256, kFramesWaves = kFramesBS / 64; // frame-kernel workgroup size (threads)
+
+// one output dwordx4 of a window (the seq kernel's per-lane stores)
+__device__ __forceinline__ void seq_store4(uint64_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w)
+{
+    typedef unsigned int v4_ __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) v4_ __attribute__((aligned(4))) G4_;
+    *(G4_ *) (uintptr_t) a = (v4_){x, y, z, w};
+}
+
 #ifndef ZMQG_SEQ_STAMPS
 #define ZMQG_SEQ_STAMPS 0 // diagnostic builds only (tools/seq_stamps.hip): per-wave s_memtime stamps into rp.clk, 64 per wave
 #endif
@@ -209,15 +178,7 @@ __device__ __forceinline__ void frame_store(uint64_t B, uint32_t w, uint32_t S, 
                                             bool last)
 {
     const uint32_t u = (uint32_t) B & 3u, up = u ? u : 4u, sh = 4u - up;
-    // (ablation 128, timing only: every window stored whole to a 64-byte-aligned
-    // place, so a frame's consecutive windows fill whole 128-byte lines)
-    const uint64_t a = (ZMQG_FRAMES_ABLATE & 128) ? ((B + 160ull) & ~127ull) + 64ull * w : B - up + 64ull * w; // aligned
-    if (ZMQG_FRAMES_ABLATE & 128) {
-        if (a + 64ull > B + S) // (never beyond the frame's own end)
-            return;
-        S = 0xffffffffu;
-        last = false;
-    }
+    const uint64_t a = B - up + 64ull * w; // aligned
     uint32_t o[17];
     o[0] = __builtin_amdgcn_alignbyte(y[0], yprev, sh);
 #pragma unroll
@@ -796,13 +757,7 @@ __device__ __forceinline__ void frames_g_impl(ZMQG_FRAMES_PARAMS)
             if (S < 64u)
                 mask_tail(x, (int) S);
         } else {
-            if (ZMQG_FRAMES_ABLATE & 4) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    x[k] = dc[k];
-            } else {
-                frame_words(dc, vin, w, S, x, DEC, act); // encode masks the ciphertext instead
-            }
+            frame_words(dc, vin, w, S, x, DEC, act); // encode masks the ciphertext instead
         }
         // r from keystream block 0 (lane 0 of the group) to the group
         if (t == 0) {
@@ -858,13 +813,7 @@ __device__ __forceinline__ void frames_g_impl(ZMQG_FRAMES_PARAMS)
         }
         if (act) {
             // Poly1305 contribution of this window
-            if (ZMQG_FRAMES_ABLATE & 1) {
-                if (w < L) {
-                    H[0] ^= c[0] ^ c[7] ^ c[13];
-                    hasH = true;
-                    lastH = w;
-                }
-            } else if (w < L) {
+            if (w < L) {
                 uint64_t a[5];
                 if (hasH) {
 #pragma unroll
@@ -959,12 +908,8 @@ __device__ __forceinline__ void frames_g_impl(ZMQG_FRAMES_PARAMS)
         const uint32_t y15 = act ? y[15] : 0u;
         const uint32_t fromleft = (uint32_t) __shfl((int) y15, (int) (lane > 0 ? lane - 1 : 0));
         const uint32_t yprev = q == 0 ? ycarry : fromleft;
-        if (act && w > 0) {
-            if (!(ZMQG_FRAMES_ABLATE & 2))
-                frame_store(B, w, S, y, yprev, w == L);
-            else
-                *(GU32 *) (uintptr_t) (B + 64ull * w) = y[0] ^ y[5] ^ y[9] ^ y[15] ^ yprev;
-        }
+        if (act && w > 0)
+            frame_store(B, w, S, y, yprev, w == L);
         ycarry = (uint32_t) __shfl((int) y15, (int) (gbase + G - 1));
     }
     // H_q * r^(kb + 4(L-1-lastH)), plus U'_L (already in tot)
@@ -1180,21 +1125,13 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src)
 // Same frame semantics, replay rule, big-frame hand-off and call state as
 // k_frames with G = 1.
 template <bool DEC, class BigOp, bool SO = false>
-#ifndef ZMQG_SEQ_WPE
-#define ZMQG_SEQ_WPE 0 // k_frames_seq: minimum waves per SIMD the register allocation must allow (0: no bound)
-#endif
-#if ZMQG_SEQ_WPE
-#define ZMQG_SEQ_ATTR __attribute__((amdgpu_waves_per_eu(ZMQG_SEQ_WPE)))
-#else
-#define ZMQG_SEQ_ATTR
-#endif
 __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
 {
     const bool lb = DEC && rp.lb_flag != nullptr;
     // The one-round look-back (below): every workgroup's header-only
     // aggregate as a self-validating record, read by each wave on its own at
     // the end.  Not in a split launch, whose other body reads the flags.
-    const bool use_rec = ZMQG_SEQ_LBREC && lb && rp.ordered && rp.lb_rec != nullptr && gridDim.x <= kFramesBS &&
+    const bool use_rec = lb && rp.ordered && rp.lb_rec != nullptr && gridDim.x <= kFramesBS &&
                          ctl.split_wg == 0; // (kernel-uniform)
     // frames this body covers: all, or (k_frames_split) the first split_n
     const uint32_t nlim = ctl.split_wg ? ctl.split_n : n;
@@ -1371,7 +1308,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
             // would be the next window's first, moved twice)
             // (the shuffle outside the condition: from an inactive lane it reads 0)
             const int fva = __shfl((int) sq_va, (int) f);
-            if (ZMQG_SEQ_SKIP5 && k == 4u && fva == 0)
+            if (k == 4u && fva == 0)
                 sq_lim[j] = 0;
         }
     }
@@ -1431,7 +1368,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
                        "s"(sq_m[2]), "s"(sq_m[3]), "s"(sq_m[4])
                      : "memory", "scc");
     };
-    if (steps > 1u && !(ZMQG_FRAMES_ABLATE & 16))
+    if (steps > 1u)
         sq_dma(1u);
 
     // Decode output in 64-byte payload chunks when every lane's payload
@@ -1442,11 +1379,12 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     // steps fill whole 128-byte lines.  Otherwise each window's 64 output
     // bytes go out at their own alignment (frame_store), two partial lines
     // per window.
-    const bool al64 = ZMQG_SEQ_AL64 && DEC && __builtin_amdgcn_ballot_w64(((uint32_t) (uintptr_t) dst & 63u) != 0u) == 0;
+    const bool al64 = DEC && __builtin_amdgcn_ballot_w64(((uint32_t) (uintptr_t) dst & 63u) != 0u) == 0;
     uint32_t yp[16]; // al64: the previous window's output words
-    // ZMQG_SEQ_COOPST (al64 decode): each lane puts its 64-byte chunk into the
-    // wave's LDS staging area, and store j of lane l writes 16 bytes (l % 4)
-    // of frame 16j + l / 4's chunk -- each instruction whole 64-byte segments
+    // Cooperative stores (the ZMQG_OPT_STREAM_OUT instantiation; decode: al64
+    // waves): each lane puts its 64-byte chunk into the wave's LDS staging
+    // area, and store j of lane l writes 16 bytes (l % 4) of frame
+    // 16j + l / 4's chunk -- each instruction whole 64-byte segments
     // of 16 frames instead of 16-byte pieces of 64 frames' segments, which
     // the L2 wrote back as partial segments (WRITE_SIZE 1.41x the payload,
     // TCC_EA0_WRREQ_64B 1.49 M requests per launch for 1.05 M segments;
@@ -1461,8 +1399,8 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     // conflict-free instructions (consecutive lanes, consecutive 16 bytes)
     // instead of 64-byte strides that put every lane on the same eight banks
     constexpr uint32_t kStgPlane = 64u * 16u + 16u;
-    __shared__ __attribute__((aligned(16))) uint8_t sq_stg[ZMQG_SEQ_COOPST && SO ? kFramesWaves * 4 * kStgPlane : 16];
-    uint8_t *const stg = sq_stg + (ZMQG_SEQ_COOPST && SO ? (threadIdx.x >> 6) * 4u * kStgPlane : 0u);
+    __shared__ __attribute__((aligned(16))) uint8_t sq_stg[SO ? kFramesWaves * 4 * kStgPlane : 16];
+    uint8_t *const stg = sq_stg + (SO ? (threadIdx.x >> 6) * 4u * kStgPlane : 0u);
     auto stg_put = [&](uint32_t k) { return stg + kStgPlane * k + 16u * lane; };
     // store j of this lane: granule lane % 4 of frame 16 j + lane / 4
     auto stg_get = [&](uint32_t j) { return stg + kStgPlane * (lane & 3u) + 16u * (16u * j + (lane >> 2)); };
@@ -1471,7 +1409,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     // (SO: the ZMQG_OPT_STREAM_OUT instantiation; al64 is wave-uniform)
     // (encode: each window's 64 bytes at frame_store's 4-byte-aligned place,
     // B - up + 64 t; the frame's last window stays per lane)
-    const bool coop = ZMQG_SEQ_COOPST && SO && (DEC ? al64 : true);
+    const bool coop = SO && (DEC ? al64 : true);
     if (coop) {
         const uint64_t cbase = DEC ? (uint64_t) (uintptr_t) dst : B - (((uint32_t) B & 3u) ? ((uint32_t) B & 3u) : 4u);
 #pragma unroll
@@ -1587,7 +1525,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         const bool act = UNI || t < nw;
         // the previous step's staged chunks, read now, stored after the
         // keystream
-        const bool had = ZMQG_SEQ_COOPST && coop && cs_pend;
+        const bool had = coop && cs_pend;
         u32x4 cg[4];
         if (had) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1596,13 +1534,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
                 cg[j] = *(const u32x4 *) stg_get(j);
         }
         uint32_t ks[16];
-        if (ZMQG_FRAMES_ABLATE & 32) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                ks[k] = key[k & 7] ^ (t * 0x9e3779b9u + k);
-        } else {
-            salsa20_block(ks, key, n0, n1, t, 0);
-        }
+        salsa20_block(ks, key, n0, n1, t, 0);
         // (the keystream is pinned here, ahead of the wait: left to itself
         // the compiler sinks it below the wait for this window's words)
 #pragma unroll
@@ -1642,12 +1574,9 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         const bool full = UNI || (pv && cp_j0 == 0u && cp_len == 64u);
         {
             Poly32 hf = h;
-            if (ZMQG_FRAMES_ABLATE & 64)
-                hf.h0 ^= cp[0] ^ cp[5] ^ cp[11];
-            else
-                // (window 0 holds two blocks; the compiler keeps t in a vector
-                // register, and a branch on it would issue both sides)
-                poly32_window_full(hf, pk, cp, UNI && __builtin_amdgcn_readfirstlane(t) == 1u);
+            // (window 0 holds two blocks; the compiler keeps t in a vector
+            // register, and a branch on it would issue both sides)
+            poly32_window_full(hf, pk, cp, UNI && __builtin_amdgcn_readfirstlane(t) == 1u);
             h.h0 = full ? hf.h0 : h.h0;
             h.h1 = full ? hf.h1 : h.h1;
             h.h2 = full ? hf.h2 : h.h2;
@@ -1658,7 +1587,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
                      : "+v"(h.h0), "+v"(h.h1), "+v"(h.h2), "+v"(h.h3), "+v"(h.h4), "+v"(ks[0]), "+v"(ks[1]), "+v"(ks[2]),
                        "+v"(ks[3]), "+v"(ks[4]), "+v"(ks[5]), "+v"(ks[6]), "+v"(ks[7]), "+v"(ks[8]), "+v"(ks[9]),
                        "+v"(ks[10]), "+v"(ks[11]), "+v"(ks[12]), "+v"(ks[13]), "+v"(ks[14]), "+v"(ks[15]));
-        if (!UNI && !(ZMQG_FRAMES_ABLATE & 64) && __builtin_amdgcn_ballot_w64(pv && !full) != 0) {
+        if (!UNI && __builtin_amdgcn_ballot_w64(pv && !full) != 0) {
             if (pv && !full)
                 poly32_window(h, pk, cp, cp_j0, cp_len);
         }
@@ -1685,20 +1614,20 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         // window t+1's covers and window t's stores, issued together after
         // the input has been consumed: the wait for the covers comes a whole
         // keystream later
-        if (!(ZMQG_FRAMES_ABLATE & 16)) {
-            if (UNI)
-                sq_dma_uni(t + 1u);
-            else if (t + 1u < steps)
-                sq_dma(t + 1u);
-        }
+        if (UNI)
+            sq_dma_uni(t + 1u);
+        else if (t + 1u < steps)
+            sq_dma(t + 1u);
         if (t < 8u)
             SEQ_STAMP(52u + t);
         const bool lastw = !UNI && act && t + 1u == nw;
         const bool no_last = UNI || __builtin_amdgcn_ballot_w64(lastw) == 0; // no lane on its last window
-        if (ZMQG_FRAMES_ABLATE & 8) {
-            if (act && y[3] == 0x12345678u && y[7] == ycarry)
-                *(GU32 *) (uintptr_t) B = y[0];
-        } else if (DEC && al64) {
+        // (ycarry and B named ahead of the chunk path's yp and dst: the closure
+        // holds its captures in order of first use, and the order of the
+        // prologue's register moves in the decode kernels follows it)
+        (void) ycarry;
+        (void) B;
+        if (DEC && al64) {
             // payload chunk t-1 (windows t-1 and t); on a lane's last window
             // also what is left of the payload (chunk t, window t alone)
             uint32_t o[16];
@@ -1717,7 +1646,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
                         seq_store4(cs_dst[j] + 64ull * (t - 2u), cg[j].x, cg[j].y, cg[j].z, cg[j].w);
                 cs_pend = false;
             }
-            if (ZMQG_SEQ_COOPST && coop && no_last) {
+            if (coop && no_last) {
                 // (every active frame's chunk is whole; a later step is
                 // certain -- the wave's longest frame has not reached its
                 // last window -- and stores them)
@@ -1766,7 +1695,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
                     cs_pend = false;
                 }
             }
-            if (!DEC && ZMQG_SEQ_COOPST && coop && no_last) {
+            if (!DEC && coop && no_last) {
                 // (each active frame's window is frame_store's whole 64
                 // bytes; a later step stores them)
                 const uint32_t u = (uint32_t) B & 3u, sh = u ? 4u - u : 0u;
@@ -1793,7 +1722,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     if (steps > 1u) {
 #pragma unroll 1
         for (uint32_t t = 1; t < steps; ++t) {
-            if (ZMQG_SEQ_UNI && t + 2u < min_nw)
+            if (t + 2u < min_nw)
                 step(std::true_type{}, t);
             else
                 step(std::false_type{}, t);
@@ -1928,7 +1857,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
 }
 
 template <bool DEC, class BigOp, bool SO = false>
-__global__ __launch_bounds__(kFramesBS) ZMQG_SEQ_ATTR void k_frames_seq(ZMQG_FRAMES_PARAMS)
+__global__ __launch_bounds__(kFramesBS) void k_frames_seq(ZMQG_FRAMES_PARAMS)
 {
     frames_seq_impl<DEC, BigOp, SO>(ZMQG_FRAMES_ARGS);
 }
@@ -1942,7 +1871,7 @@ __global__ __launch_bounds__(kFramesBS) ZMQG_SEQ_ATTR void k_frames_seq(ZMQG_FRA
 // one-session replay look-back runs across the two bodies unchanged; the
 // host launches this only when the grid is co-resident (no tickets).
 template <bool DEC, int GT, class BigOp>
-__global__ __launch_bounds__(kFramesBS) ZMQG_SEQ_ATTR void k_frames_split(ZMQG_FRAMES_PARAMS)
+__global__ __launch_bounds__(kFramesBS) void k_frames_split(ZMQG_FRAMES_PARAMS)
 {
     if (blockIdx.x < ctl.split_wg)
         frames_seq_impl<DEC, BigOp>(ZMQG_FRAMES_ARGS);

@@ -31,20 +31,17 @@
 // bytes beyond 128 are copied to [0, 16) before the next (even) window is
 // written, so [64(t&1), +64) always holds window t's aligned granules (its
 // first u bytes from window t-1).
-// Measured alternatives: 64-byte-aligned runs
-// (ZMQG_LDS_SECTOR=64) cut the write traffic WRITE_SIZE reports from 1.71x to
-// 1.38x the payload but were 5-10 % slower (the ring copies grow to 64
-// bytes); one input buffer refilled right after it is read (ZMQG_LDS_INBUF=1)
-// was slower again (the LDS reads are waited for before the DMA).
+// Measured alternatives, not kept: output runs aligned
+// to 64 bytes instead of 16 cut the write traffic WRITE_SIZE reports from
+// 1.71x to 1.38x the payload but were 5-10 % slower (the ring copies grow to
+// 64 bytes); one input buffer per wave, refilled right after it is read, was
+// slower again (the LDS reads are waited for before the DMA).
 #pragma once
 
 #include "curve_frames.hpp"
 
 namespace zmqg {
 
-#ifndef ZMQG_LDS_SECTOR
-#define ZMQG_LDS_SECTOR 16 // output runs are aligned to this many bytes (16 or 64)
-#endif
 // Issue priority by phase.  Two waves share each SIMD here (two workgroups
 // per CU) and the arbiter favours the older one, so a wave that reaches its
 // descriptor and key loads, a step's DMA and stores, or its epilogue while the
@@ -55,30 +52,12 @@ namespace zmqg {
 // sessions) 9.87-9.89 ms per encode+decode against 11.12-11.18 for no
 // priorities on one box; 3/1 gave 9.91-10.26, 2/0 10.52-10.56
 // (DESIGN.md section 3.1).
-#ifndef ZMQG_LDS_PRIO
-#define ZMQG_LDS_PRIO 2 // priority while issuing memory work / during the keystream: 0 none, 1 3/1, 2 3/0, 3 2/0
-#endif
-#define LDS_PRIO_MEM (ZMQG_LDS_PRIO == 3 ? 2 : 3)
-#define LDS_PRIO_KS (ZMQG_LDS_PRIO == 1 ? 1 : 0)
-// (s_setprio takes an immediate)
-#define LDS_PRIO(lv)                                                                                   \
-    do {                                                                                               \
-        if (ZMQG_LDS_PRIO)                                                                             \
-            __builtin_amdgcn_s_setprio(lv);                                                            \
-    } while (0)
-#ifndef ZMQG_LDS_ALIGN64
-#define ZMQG_LDS_ALIGN64 1 // cooperative stores as 64-byte-aligned pieces (0: the windows' own granules)
-#endif
-#ifndef ZMQG_LDS_INBUF
-#define ZMQG_LDS_INBUF 2 // input buffers per wave (1: refilled right after it is read)
-#endif
-constexpr uint32_t kStSector = ZMQG_LDS_SECTOR;
-constexpr uint32_t kStNIn = ZMQG_LDS_INBUF;
-static_assert(kStSector == 16 || kStSector == 64, "output sector");
-static_assert(kStNIn == 1 || kStNIn == 2, "input buffers");
+constexpr int kStPrioMem = 3, kStPrioKs = 0; // while issuing memory work / during the keystream
+constexpr uint32_t kStSector = 16;                              // output runs are aligned to this many bytes
+constexpr uint32_t kStNIn = 2;                                  // input buffers per wave
 constexpr uint32_t kStRing = 128 + kStSector;                   // output ring slot
 constexpr uint32_t kStInBuf = 64 * kStIn;                       // one input buffer per wave
-constexpr uint32_t kStWave = kStNIn * kStInBuf + 64 * kStRing;  // 19,456 bytes per wave (16, 2)
+constexpr uint32_t kStWave = kStNIn * kStInBuf + 64 * kStRing;  // 19,456 bytes per wave
 
 typedef __attribute__((address_space(1))) void StGVoid;
 
@@ -125,7 +104,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
     __shared__ __attribute__((aligned(16))) uint8_t st_lds[kFramesWaves * kStWave];
     const bool lb = DEC && rp.lb_flag != nullptr;
     SEQ_STAMP(0u);
-    LDS_PRIO(LDS_PRIO_MEM);
+    __builtin_amdgcn_s_setprio(kStPrioMem);
     __shared__ unsigned long long sh_wmax[kFramesWaves];
     __shared__ CallState sh_cs;
     const bool use_ticket = lb && !rp.ordered; // (kernel-uniform)
@@ -289,7 +268,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
             la[j] = shfl_u64(Ab, f) + lrel[j];
             llim[j] = (uint32_t) __shfl((int) lim, (int) f);
             const int fva = __shfl((int) va, (int) f); // (k_frames_seq's notes)
-            if (ZMQG_SEQ_SKIP5 && k == 4u && fva == 0)
+            if (k == 4u && fva == 0)
                 llim[j] = 0;
         }
     }
@@ -315,7 +294,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
         // (every frame's last window the wave's last: a lane past its frame
         // would overwrite its ring, and the tail read below, with later steps)
         const bool ok = valid && S >= 80u && nw == steps && (lane == 0 || Bp + Sp == B);
-        merge = kStSector == 16 && __builtin_amdgcn_ballot_w64(!ok) == 0;
+        merge = __builtin_amdgcn_ballot_w64(!ok) == 0;
     }
     // store pair j: granule lane % 4 of frame 16j + lane / 4 of each window; its
     // frame's cooperatively stored bytes are ring-relative [slo, shi) (decode:
@@ -337,7 +316,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
     {
         const uint64_t Gb = B - ub;
         const uint32_t d = (64u - ((uint32_t) Gb & 63u)) & 63u;
-        const int32_t sh = ZMQG_LDS_ALIGN64 && d > ub ? (int32_t) d - 64 : 0;
+        const int32_t sh = d > ub ? (int32_t) d - 64 : 0;
         uint32_t slo = ub + (DEC ? 33u : 32u), shi = S ? ub + S : 0u;
         if (merge) {
             slo = (slo + 15u) & ~15u;
@@ -358,7 +337,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
     const uint32_t wlds_off =
         __builtin_amdgcn_readfirstlane((uint32_t) (uintptr_t) (StLdsVoid *) wlds); // the wave's LDS byte offset
     auto dma = [&](uint32_t t) {
-        const uint32_t b = wlds_off + (kStNIn == 2 ? (t & 1u) * kStInBuf : 0u);
+        const uint32_t b = wlds_off + (t & 1u) * kStInBuf;
 #pragma unroll
         for (uint32_t j = 0; j < 5; ++j)
             if (64u * t + lrel[j] < llim[j])
@@ -388,7 +367,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
                 *(GU4 *) (uintptr_t) (sa[j] + (int64_t) (64 * (int32_t) t + ssh4[j])) = g[j];
             partm |= part ? 1u << j : 0u;
         }
-        if (!(ZMQG_FRAMES_ABLATE & 512) && __builtin_amdgcn_ballot_w64(partm != 0) != 0) {
+        if (__builtin_amdgcn_ballot_w64(partm != 0) != 0) {
 #pragma unroll
             for (uint32_t j = 0; j < 4; ++j)
                 if ((partm >> j) & 1u) {
@@ -404,13 +383,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
         ring_store(t, g);
     };
     auto ring_spill = [&]() {
-        u32x4 o[kStSector / 16];
-#pragma unroll
-        for (uint32_t q = 0; q < kStSector / 16; ++q)
-            o[q] = *(const u32x4 *) (myring + 128 + 16 * q);
-#pragma unroll
-        for (uint32_t q = 0; q < kStSector / 16; ++q)
-            *(u32x4 *) (myring + 16 * q) = o[q];
+        *(u32x4 *) myring = *(const u32x4 *) (myring + 128); // (kStSector bytes: one granule)
     };
     // window t's output bytes y -> the ring
     auto ring_put = [&](uint32_t t, const uint32_t y[16]) {
@@ -425,7 +398,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
         dma(1u);
 
     SEQ_STAMP(1u);
-    LDS_PRIO(LDS_PRIO_KS);
+    __builtin_amdgcn_s_setprio(kStPrioKs);
     // ---- step 0: window 0 (Poly1305 key, first 32 ciphertext bytes, header)
     PolyKey32 pk;
     Poly32 h = {0, 0, 0, 0, 0};
@@ -497,13 +470,13 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
         // stores go out before the keystream, so a whole window hides them
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        LDS_PRIO(LDS_PRIO_MEM);
+        __builtin_amdgcn_s_setprio(kStPrioMem);
         if (t < 8u)
             SEQ_STAMP(44u + t);
         const bool act = t < nw;
         uint32_t x[16];
         {
-            const uint8_t *const p = wlds + (kStNIn == 2 ? (t & 1u) * kStInBuf : 0u) + kStIn * lane + va;
+            const uint8_t *const p = wlds + (t & 1u) * kStInBuf + kStIn * lane + va;
 #pragma unroll
             for (uint32_t q = 0; q < 4; ++q) {
                 const u32x4 v = *(const u32x4_u1 *) (p + 16u * q);
@@ -515,22 +488,14 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
         }
         u32x4 g[4];
         ring_get(t - 1u, g);
-        if (kStNIn == 1) // the input buffer is read before the next window's DMA refills it
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (t + 1u < steps)
             dma(t + 1u);
         ring_store(t - 1u, g);
-        LDS_PRIO(LDS_PRIO_KS);
+        __builtin_amdgcn_s_setprio(kStPrioKs);
         if (t < 8u)
             SEQ_STAMP(52u + t);
         uint32_t ks[16];
-        if (ZMQG_FRAMES_ABLATE & 32) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                ks[k] = key[k & 7] ^ (t * 0x9e3779b9u + k);
-        } else {
-            salsa20_block(ks, key, n0, n1, t, 0);
-        }
+        salsa20_block(ks, key, n0, n1, t, 0);
         // The previous window's MAC (its ciphertext is in cp), the four-block
         // form for every lane, unconditionally, in the keystream's basic block
         // (see k_frames_seq); lanes whose window was not four full blocks keep
@@ -539,10 +504,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
         const bool full = pv && cp_j0 == 0u && cp_len == 64u;
         {
             Poly32 hf = h;
-            if (ZMQG_FRAMES_ABLATE & 64)
-                hf.h0 ^= cp[0] ^ cp[5] ^ cp[11];
-            else
-                poly32_window_full(hf, pk, cp);
+            poly32_window_full(hf, pk, cp);
             h.h0 = full ? hf.h0 : h.h0;
             h.h1 = full ? hf.h1 : h.h1;
             h.h2 = full ? hf.h2 : h.h2;
@@ -553,7 +515,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
         for (int k = 0; k < 16; ++k)
             asm volatile("" : "+v"(ks[k]));
         asm volatile("" : "+v"(h.h0), "+v"(h.h1), "+v"(h.h2), "+v"(h.h3), "+v"(h.h4));
-        if (!(ZMQG_FRAMES_ABLATE & 64) && __builtin_amdgcn_ballot_w64(pv && !full) != 0) {
+        if (__builtin_amdgcn_ballot_w64(pv && !full) != 0) {
             if (pv && !full)
                 poly32_window(h, pk, cp, cp_j0, cp_len);
         }
@@ -582,7 +544,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
             SEQ_STAMP(36u + t);
     }
     SEQ_STAMP(60u);
-    LDS_PRIO(LDS_PRIO_MEM);
+    __builtin_amdgcn_s_setprio(kStPrioMem);
     if (steps > 0) {
         // the last window's granules, and the granules its last ub bytes
         // spill into (odd window: bytes beyond ring byte 128, copied first)
@@ -682,13 +644,7 @@ __global__ __launch_bounds__(kFramesBS) void k_frames_lds(
     } else if (!DEC) {
         // "\x07MESSAGE" || nonce || tag: wire bytes 0..31 (the rest went out cooperatively)
         uint32_t o[16] = {0x53454d07u, 0x45474153u, n0, n1, tag[0], tag[1], tag[2], tag[3]};
-        if (ZMQG_FRAMES_ABLATE & 1024) { // (timing only: two aligned dwordx4 at the granule below)
-            GU4 *q = (GU4 *) (uintptr_t) ((uint64_t) (uintptr_t) dst & ~15ull);
-            q[0] = (u32x4){o[0], o[1], o[2], o[3]};
-            q[1] = (u32x4){o[4], o[5], o[6], o[7]};
-        } else {
-            store_bytes_c<32>(dst, o);
-        }
+        store_bytes_c<32>(dst, o);
     } else {
         if (lb && !(vn > excl))
             status = ZMQG_ERR_INVALID_SEQUENCE; // src/curve_mechanism_base.cpp:99-104 (before the MAC)

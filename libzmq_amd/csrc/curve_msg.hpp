@@ -182,25 +182,8 @@ __device__ __forceinline__ fe fe_wave_sum(const fe &x)
 // The launch's completion word: every lane's writes reach memory (system
 // scope: the results sit in mapped host memory), then lane 0 sets it.  The
 // host polls it instead of waiting for the stream (zmqg_*_msg).
-#ifndef ZMQG_MSG_ABLATE
-#define ZMQG_MSG_ABLATE 0 // (diagnostic builds only: 1 full system fence, 2 no fence, 4 no Salsa20,
-                          // 8 no Poly1305 tree, 16 no output stores, 32 no input loads)
-#endif
 __device__ __forceinline__ void msg_done(uint32_t *done)
 {
-    if (ZMQG_MSG_ABLATE & 2) {
-        __syncthreads();
-        if (threadIdx.x == 0)
-            __hip_atomic_store(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
-    if (ZMQG_MSG_ABLATE & 1) { // (the round-4 default before: a full system fence, acquire side included)
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0)
-            __hip_atomic_store(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
     // every thread's writes released at system scope (the host reads them
     // after seeing the word; nothing is read back here, so no acquire), then
     // the word
@@ -297,7 +280,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg(MsgArgs a, MsgInline<CAP> d
             st[32 + tid] = (uint8_t) (hw[tid >> 2] >> (8 * (tid & 3)));
         if (CAP)
             msg_inline_lds(st + 32 + hl, d, a.len, tid);
-        else if (!(ZMQG_MSG_ABLATE & 32))
+        else
             msg_load_lds(st + 32 + hl, a.in, a.len, tid);
         nc = a.nonce;
         n0 = bswap32((uint32_t) (nc >> 32));
@@ -308,7 +291,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg(MsgArgs a, MsgInline<CAP> d
         const uint32_t L = a.len;
         if (CAP)
             msg_inline_lds(st, d, L, tid);
-        else if (!(ZMQG_MSG_ABLATE & 32))
+        else
             msg_load_lds(st, a.in, L, tid);
         m = L >= 33u ? L - 32u : 0u;
     }
@@ -354,12 +337,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg(MsgArgs a, MsgInline<CAP> d
     const uint32_t ic = q == 0 ? blk : q == 1 ? key[6] : q == 2 ? key[1] : n1;
     const uint32_t id = q == 0 ? key[5] : q == 1 ? key[0] : q == 2 ? n0 : key[4];
     uint32_t ka = sig, kb = ib, kc = ic, kd = id;
-    if (ZMQG_MSG_ABLATE & 4) {
-        ka ^= blk * 0x9e3779b9u;
-        kc ^= kb;
-    } else {
-        salsa20_quad(ka, kb, kc, kd);
-    }
+    salsa20_quad(ka, kb, kc, kd);
     ka += sig;
     kb += ib;
     kc += ic;
@@ -423,7 +401,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg(MsgArgs a, MsgInline<CAP> d
     uint32_t levels = 0;
     while ((1u << levels) < nl)
         ++levels;
-    const bool scan = levels && !(ZMQG_MSG_ABLATE & 8);
+    const bool scan = levels != 0;
     const uint32_t wv = tid >> 6;
     const uint32_t P = DEC && a.len >= 33u ? a.len - 33u : 0u;
     fe h = fe_zero();
@@ -486,7 +464,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg(MsgArgs a, MsgInline<CAP> d
             for (int i = 0; i < 5; ++i)
                 sh_pw[64 * i + lane] = pw.l[i];
         }
-    } else if (status == 0 && !(ZMQG_MSG_ABLATE & 16)) { // waves 1 and 2
+    } else if (status == 0) { // waves 1 and 2
         const uint32_t j = tid - 64;
         if (!DEC) {
             // "\x07MESSAGE" || nonce, then the ciphertext
@@ -522,7 +500,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg(MsgArgs a, MsgInline<CAP> d
 
     // ---- 4. results
     if (!DEC) {
-        if (status == 0 && !(ZMQG_MSG_ABLATE & 16) && tid < 16) {
+        if (status == 0 && tid < 16) {
             const uint32_t w = tid < 4 ? tag[0] : tid < 8 ? tag[1] : tid < 12 ? tag[2] : tag[3];
             a.out[16 + tid] = (uint8_t) (w >> (8 * (tid & 3u)));
         }
@@ -537,7 +515,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg(MsgArgs a, MsgInline<CAP> d
     if (wv == 0) {
         if (status == 0 && ((tag[0] ^ st_w[4]) | (tag[1] ^ st_w[5]) | (tag[2] ^ st_w[6]) | (tag[3] ^ st_w[7])))
             status = ZMQG_ERR_CRYPTOGRAPHIC; // src/curve_mechanism_base.cpp:277-281
-        if (status != 0 && !(ZMQG_MSG_ABLATE & 16))
+        if (status != 0)
             msg_zero_g<64>(a.out, P, lane);
         if (tid == 0) {
             // msg_t::more | msg_t::command (curve_mechanism_base.cpp:276)

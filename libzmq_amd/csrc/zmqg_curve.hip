@@ -63,27 +63,6 @@
 #include "curve_fwd_route.hpp"
 #include "curve_ws.hpp"
 
-#ifndef ZMQG_ABLATE
-#define ZMQG_ABLATE 0
-#endif
-#ifndef ZMQG_STAMPS
-#define ZMQG_STAMPS 0
-#endif
-#if ZMQG_STAMPS // diagnostic build only: per-wave phase timestamps (tools/stamps.py)
-__device__ unsigned long long zmqg_stamp_buf[1 << 17];
-__device__ unsigned int zmqg_stamp_ctr;
-#define ZSTAMP(k)                                                                   \
-    do {                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-        unsigned long long t_;                                                      \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-        st_[k] = t_;                                                                \
-    } while (0)
-#else
-#define ZSTAMP(k) do { } while (0)
-#endif
-
 using namespace zmqg;
 
 namespace {
@@ -1499,20 +1478,13 @@ __global__ __launch_bounds__(256) void k_post(ZState *__restrict__ zs, const Pos
 
 // The big-frame list (positions 0 .. n-1, built by the frame kernel's head
 // calls) is read from the call state: n = entries, total = body chunks.
-template <bool DEC>
+//
 // Issue priority by phase, as in k_frames_lds (curve_frames_lds.hpp): 3 while
 // a wave issues a tile's loads, DMA and stores, 0 over its keystream, MAC and
 // finish.  Configs 3 / 5 on one box, two alternating rounds: 538 / 534 and
 // 590.5 / 590.2 GiB/s against 527 / 528 and 586 / 588 without (the body
 // kernel already keeps the SIMDs' VALU ~98 % busy at config 5).
-#ifndef ZMQG_BODY_PRIO
-#define ZMQG_BODY_PRIO 1 // 0: no priorities
-#endif
-#define BODY_PRIO(lv)                                                                                  \
-    do {                                                                                               \
-        if (ZMQG_BODY_PRIO)                                                                            \
-            __builtin_amdgcn_s_setprio(lv);                                                            \
-    } while (0)
+template <bool DEC>
 __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_body(
     ZState *__restrict__ zs, const uint32_t *__restrict__ chunk_end,
     const FrameHot *__restrict__ hot, const FramePow *__restrict__ pw, const FrameFin *__restrict__ fin,
@@ -1564,16 +1536,11 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
 
 #pragma unroll 1
     for (uint32_t t = tb; t < te; ++t) {
-#if ZMQG_STAMPS
-        unsigned long long st_[8];
-#endif
-        ZSTAMP(0);
         uint8_t *const cb = wlds + ((t - tb) & 1) * kBufLds;
         uint8_t *const nb = wlds + (((t - tb) & 1) ^ 1) * kBufLds;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // tile t's DMA (and everything before it)
         wave_lds_fence();
-        ZSTAMP(1);
-        BODY_PRIO(3);
+        __builtin_amdgcn_s_setprio(3);
         const bool has_next = t + 1 < te;
         // ---- issue: next tile's records, the chunk-end window after it
         const uint32_t gn = 64 * (t + 1) + lane;
@@ -1619,14 +1586,8 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
                 w[q] = __builtin_amdgcn_alignbyte(d[q + 1], d[q], si);
             if (nv < 64)
                 mask_tail(w, nv);
-#if ZMQG_ABLATE == 2 // timing experiment only: memory traffic without keystream/MAC work
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                ks[q] = tw * 16 + q;
-#else
             salsa20_block(ks, cur.k, cur.n0, cur.n1, 1 + 2 * cur.c + tw, 0);
-#endif
-            if (DEC && ZMQG_ABLATE != 2) {
+            if (DEC) {
                 if (__all(nv == 64))
                     poly32_window_full(h, pk, w);
                 else
@@ -1637,15 +1598,12 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
                 w[q] ^= ks[q];
             if (nv < 64)
                 mask_tail(w, nv);
-            if (!DEC && ZMQG_ABLATE != 2) {
+            if (!DEC) {
                 if (__all(nv == 64))
                     poly32_window_full(h, pk, w);
                 else
                     poly32_window(h, pk, w, 0u, (uint32_t) nv);
             }
-#if ZMQG_ABLATE == 2
-            h.h0 ^= w[0];
-#endif
             if (tw + 1 < nwin) { // read ahead before this window's output overwrites it
 #pragma unroll
                 for (int q = 0; q < 17; ++q)
@@ -1666,11 +1624,10 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
                     outw[16 * tw + 16] = __builtin_amdgcn_alignbyte(0u, w[15], 4 - so);
             }
         };
-        BODY_PRIO(0);
+        __builtin_amdgcn_s_setprio(0);
         if (nwin > 0)
             window(0);
-        BODY_PRIO(3);
-        ZSTAMP(2);
+        __builtin_amdgcn_s_setprio(3);
         // ---- setup: next tile's params and its DMA; locate the tile after it
         // (on the wave's last tile this sets up an all-idle tile: no DMA)
         TileLane nx;
@@ -1678,16 +1635,13 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
             const uint64_t nsrc = tile_setup<DEC>(nx, Rn, has_next && gn < total, lkn, gn, cur, false);
             uint64_t a0;
             const bool uni = tile_uniform(nx.key, nx.L, nsrc, a0);
-            if (ZMQG_ABLATE == 6) { // (timing experiments only)
-            } else if (uni) {
+            if (uni)
                 tile_dma_uni(nb, a0, U);
-            } else {
+            else
                 tile_dma(nb, nsrc, nx.L);
-            }
         }
         const FrameLook lk2 = window_find(ce2, lo2, n, 64 * (t + 2) + lane);
-        ZSTAMP(3);
-        BODY_PRIO(0);
+        __builtin_amdgcn_s_setprio(0);
         if (nwin > 1)
             window(1);
         fe hf = poly32_to_fe(h);
@@ -1696,10 +1650,8 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
         for (int q = 0; q < 5; ++q)
             v[q] = hf.l[q];
         wave_lds_fence();
-        ZSTAMP(4);
-        BODY_PRIO(3);
+        __builtin_amdgcn_s_setprio(3);
         // ---- store: coalesced interior granules, then this lane's edges
-        if (ZMQG_ABLATE != 5) // (timing experiments only)
         {
             uint64_t d0;
             if (tile_uniform(cur.key, L, cur.dst, d0))
@@ -1707,7 +1659,7 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
             else
                 tile_store_interior(cb, cur.dst, L);
         }
-        if (L > 0 && ZMQG_ABLATE != 3) {
+        if (L > 0) {
             const uint32_t end = dO + L;
             GU8 *gbase = (GU8 *) (uintptr_t) (cur.dst - dO);
             const uint32_t ql = end >> 4, el = end & 15; // granule of the last byte / its valid bytes
@@ -1735,8 +1687,7 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
                     store_granule_range(gbase + 16 * ql, 0, hi, gv);
             }
         }
-        ZSTAMP(5);
-        BODY_PRIO(0);
+        __builtin_amdgcn_s_setprio(0);
         // ---- finish: Poly1305 combine and tag / status
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -1746,7 +1697,7 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
         // one goes on as the carry, or, on the wave's last tile, is moved to
         // the frame's end and combined.
         bool first = false, carried = false;
-        if (ZMQG_ABLATE != 4) {
+        {
             const uint32_t k0 = __builtin_amdgcn_readfirstlane(cur.key);
             if (__all(cur.key == k0 && k0 != kIdle)) { // one frame's segment: plain wave sum
                 wave_sum_all(v);
@@ -1841,15 +1792,6 @@ __global__ __launch_bounds__(kBodyThreads) __attribute__((amdgpu_waves_per_eu(2)
                 }
             }
         }
-#if ZMQG_STAMPS
-        ZSTAMP(6);
-        if (lane == 0) {
-            const unsigned int slot = atomicAdd(&zmqg_stamp_ctr, 1u);
-            if (slot < (1u << 17) / 8)
-                for (int q = 0; q < 7; ++q)
-                    zmqg_stamp_buf[slot * 8 + q] = st_[q] - st_[0];
-        }
-#endif
         cur = nx;
         lkn = lk2;
     }
@@ -2307,28 +2249,6 @@ int zmqg_ctx_get_profile(zmqg_ctx *ctx, int kind, double *ms_total, uint64_t *la
     ctx->prof[kind].clear();
     return 0;
 }
-
-#if ZMQG_STAMPS
-// diagnostic build only: copy out (and reset) the per-wave phase stamps
-int zmqg_debug_stamps(unsigned long long *out, uint32_t max_records, uint32_t *count)
-{
-    unsigned int n = 0;
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&n, HIP_SYMBOL(zmqg_stamp_ctr), sizeof n) != hipSuccess)
-        return -EIO;
-    if (n > (1u << 17) / 8)
-        n = (1u << 17) / 8;
-    if (n > max_records)
-        n = max_records;
-    if (n && hipMemcpyFromSymbol(out, HIP_SYMBOL(zmqg_stamp_buf), (size_t) n * 8 * sizeof(unsigned long long)) !=
-                 hipSuccess)
-        return -EIO;
-    unsigned int z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(zmqg_stamp_ctr), &z, sizeof z) != hipSuccess)
-        return -EIO;
-    *count = n;
-    return 0;
-}
-#endif
 
 const char *zmqg_last_error(zmqg_ctx *ctx)
 {

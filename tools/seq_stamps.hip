@@ -88,9 +88,7 @@ int main(int argc, char **argv)
             rp.lb_flag = d_v + 2 + n;
             rp.lb_agg = rp.lb_flag + lbw;
             rp.lb_inc = rp.lb_agg + lbw;
-#ifdef ZMQG_SEQ_LBREC
             rp.lb_rec = rp.lb_inc + lbw;
-#endif
             rp.ordered = 1;
         }
         for (int rep = 0; rep < STAMP_REPS; ++rep) {
