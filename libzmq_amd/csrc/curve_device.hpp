@@ -551,6 +551,17 @@ __device__ __forceinline__ void mask_tail(uint32_t w[16], int nv)
 // Load bytes p[0 .. nv) (0 <= nv <= 64, any alignment) as 16 little-endian
 // words, zero beyond nv.  Only 4-byte words that hold a valid byte are read,
 // so the access never leaves the 4-byte granules of the valid range.
+// (the raw part: the aligned words q[0 .. ND) of which those that hold one of
+// the nv bytes from byte sh of q[0] on are read, the others zero)
+template <int ND>
+__device__ __forceinline__ void load_window_raw(const uint32_t *q, uint32_t sh, int nv, uint32_t d[ND])
+{
+    const int nd = (int) ((sh + (uint32_t) nv + 3) >> 2);
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+        d[i] = i < nd ? q[i] : 0u;
+}
+
 __device__ __forceinline__ void load_window(const uint8_t *p, int nv, uint32_t w[16])
 {
     const uint32_t sh = (uint32_t) ((uintptr_t) p & 3);
@@ -562,10 +573,7 @@ __device__ __forceinline__ void load_window(const uint8_t *p, int nv, uint32_t w
             d[i] = q[i];
         d[16] = sh ? q[16] : 0u;
     } else {
-        const int nd = (int) ((sh + (uint32_t) nv + 3) >> 2);
-#pragma unroll
-        for (int i = 0; i < 17; ++i)
-            d[i] = i < nd ? q[i] : 0u;
+        load_window_raw<17>(q, sh, nv, d);
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i)
@@ -687,8 +695,10 @@ __device__ __forceinline__ void store_bytes_c(uint8_t *p, const uint32_t w[16])
 // and one dword when p is not 4-byte aligned (a word holding a byte of the
 // range never crosses into a page the range does not touch) -- a fixed
 // sequence where load_window's runtime length issues one load per word.
+// (the raw part: the aligned words d[0 .. NV/4], the last one zero when p is
+// 4-byte aligned)
 template <int NV>
-__device__ __forceinline__ void load_bytes_c(const uint8_t *p, uint32_t w[NV / 4])
+__device__ __forceinline__ void load_bytes_raw(const uint8_t *p, uint32_t d[NV / 4 + 1])
 {
     static_assert(NV % 16 == 0 && NV >= 16 && NV <= 48, "whole granules");
     typedef __attribute__((address_space(1))) const uint32_t GCU32_;
@@ -698,7 +708,6 @@ __device__ __forceinline__ void load_bytes_c(const uint8_t *p, uint32_t w[NV / 4
     const uint32_t sh = (uint32_t) a & 3u;
     const uint64_t q = a - sh;
     constexpr int ND = NV / 4;
-    uint32_t d[ND + 1];
 #pragma unroll
     for (int g = 0; g < ND / 4; ++g) {
         const u32x4_ t = *(GCU4a4_ *) (uintptr_t) (q + 16u * g);
@@ -708,6 +717,15 @@ __device__ __forceinline__ void load_bytes_c(const uint8_t *p, uint32_t w[NV / 4
         d[4 * g + 3] = t.w;
     }
     d[ND] = sh ? *(GCU32_ *) (uintptr_t) (q + 4u * ND) : 0u;
+}
+
+template <int NV>
+__device__ __forceinline__ void load_bytes_c(const uint8_t *p, uint32_t w[NV / 4])
+{
+    constexpr int ND = NV / 4;
+    uint32_t d[ND + 1];
+    load_bytes_raw<NV>(p, d);
+    const uint32_t sh = (uint32_t) (uintptr_t) p & 3u;
 #pragma unroll
     for (int k = 0; k < ND; ++k)
         w[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);

@@ -440,6 +440,13 @@ __device__ __forceinline__ void call_state_count(ZState *zs)
         (void) __hip_atomic_fetch_add(&zs->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// (k_frames_seq without a ticket: every wave reads the call state itself,
+// beside its descriptors -- the previous call wrote the values, the kernel
+// boundary makes them visible -- so no wave waits for thread 0's reads and a
+// barrier ahead of its first window; thread 0 counts the workgroup behind
+// the barrier that follows window 0's keystream, when every wave has its
+// values.  One count per wave instead, 1,024 atomics on one address at the
+// config-2 shape, held every wave ~9 k cycles at its next wait for memory.)
 template <bool DEC>
 __device__ __forceinline__ void call_state_end(ZState *zs, const FrameCtl &ctl, const CallState &c, uint32_t n)
 {
@@ -554,7 +561,9 @@ struct NoBigFrames {
 // an entry in this call's big-frame list).
 // zs: the context's call state (see ZState); decode with rp.lb_flag set
 // applies the one-session replay rule in this kernel.
-#define ZMQG_FRAMES_PARAMS                                                                                    \
+// (FramesKernarg, below, mirrors this list for k_frames_seq's argument
+// prefetch: a parameter added here is added there.)
+#define ZMQG_FRAMES_PARAMS                                                                                   \
     uint32_t n, const uint32_t *__restrict__ sid, const uint64_t *__restrict__ nonce,                             \
         const uint8_t *__restrict__ flags, const uint64_t *__restrict__ in_off, const uint32_t *__restrict__ len, \
         const uint8_t *__restrict__ in, const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out,          \
@@ -1122,11 +1131,55 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src)
     return ((uint64_t) hi << 32) | lo;
 }
 
+// The explicit kernel arguments of ZMQG_FRAMES_PARAMS as the kernarg segment
+// lays them out (each at its natural alignment); the launch's grid size
+// follows them.
+template <class BigOp>
+struct FramesKernarg {
+    uint32_t n;
+    const void *sid, *nonce, *flags, *in_off, *len, *in, *out_off, *out, *sessions;
+    uint32_t max_sessions, max_stream;
+    void *flags_out, *status_out;
+    ReplayOut rp;
+    BigOp big;
+    ZState *zs;
+    FrameCtl ctl;
+};
+
+// One dword of every 64-byte line of the first BYTES + 8 bytes of the kernarg
+// segment, asked for in one burst of scalar loads and waited for once: the
+// scalar cache is cold at kernel start, and the loads the compiler makes
+// from the same lines afterwards hit it.
+template <size_t BYTES>
+__device__ __forceinline__ void kernarg_touch()
+{
+    typedef __attribute__((address_space(4))) const uint32_t KA32;
+    KA32 *const ka = (KA32 *) __builtin_amdgcn_kernarg_segment_ptr();
+    constexpr int NL = (int) ((BYTES + 8 + 63) / 64);
+    uint32_t t[NL];
+#pragma unroll
+    for (int q = 0; q < NL; ++q)
+        t[q] = ka[16 * q];
+    static_assert(NL >= 1 && NL <= 8, "one statement's operands");
+    auto at = [&](int q) { return t[q < NL ? q : NL - 1]; };
+    asm volatile("" ::"s"(at(0)), "s"(at(1)), "s"(at(2)), "s"(at(3)), "s"(at(4)), "s"(at(5)), "s"(at(6)), "s"(at(7)));
+}
+
 // Same frame semantics, replay rule, big-frame hand-off and call state as
 // k_frames with G = 1.
 template <bool DEC, class BigOp, bool SO = false>
 __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
 {
+    // Every 64-byte line of the kernel's arguments is asked for at once: left
+    // to the compiler they are read in groups as the code needs them, each
+    // group that opens a new line a scalar-cache miss of its own in series.
+#if ZMQG_SEQ_STAMPS
+    const unsigned long long clk_entry = __builtin_amdgcn_s_memtime();
+#endif
+    kernarg_touch<sizeof(FramesKernarg<BigOp>)>();
+#if ZMQG_SEQ_STAMPS
+    const unsigned long long clk_args = __builtin_amdgcn_s_memtime();
+#endif
     const bool lb = DEC && rp.lb_flag != nullptr;
     // The one-round look-back (below): every workgroup's header-only
     // aggregate as a self-validating record, read by each wave on its own at
@@ -1136,15 +1189,28 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     // frames this body covers: all, or (k_frames_split) the first split_n
     const uint32_t nlim = ctl.split_wg ? ctl.split_n : n;
     SEQ_STAMP(0u);
+#if ZMQG_SEQ_STAMPS
+    // (the clock at entry and with the arguments there: before rp.clk is known)
+    if (rp.clk && (threadIdx.x & 63u) == 0) {
+        rp.clk[64ull * (blockIdx.x * kFramesWaves + (threadIdx.x >> 6)) + 20u] = clk_entry;
+        rp.clk[64ull * (blockIdx.x * kFramesWaves + (threadIdx.x >> 6)) + 21u] = clk_args;
+    }
+#endif
     __shared__ unsigned long long sh_wmax[kFramesWaves];
     __shared__ CallState sh_cs;
     const bool use_ticket = lb && !rp.ordered; // (kernel-uniform)
+    // thread 0 reads the call state for its workgroup (call_state_begin):
+    // with tickets, and in a split launch, whose other body counts workgroups
+    const bool relay = use_ticket || ctl.split_wg != 0; // (kernel-uniform)
     const uint32_t lane = threadIdx.x & 63u;
 
-    // The frame's descriptors, session key and first window.  Without a
-    // look-back ticket to take, the workgroup's frames are known at entry, so
-    // these loads go out before the call state's round trip (thread 0's
-    // reads, joined by the barrier below) instead of after it.
+    // The frame's descriptors, session key and first window, in two groups
+    // of loads: what depends on the frame's index alone (group A), and what
+    // depends on those (group B: the key, then what window 0's keystream and
+    // the header checks read, then what is used behind the keystream).  The
+    // groups are held in place by the statements between them, and nothing of
+    // group B is waited for before its first use.  Without a look-back ticket
+    // to take, the workgroup's frames are known at entry.
     uint32_t i = 0, ii = 0, s = 0, L_in = 0;
     bool valid = false, sid_ok = false, over = false;
     const uint8_t *src = nullptr;
@@ -1154,76 +1220,132 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     uint64_t A = 0, B = 0;
     int32_t status = 0;
     uint32_t hw[3] = {0, 0, 0};
-    uint32_t x0[16]; // window 0's stream words (decode: the wire; encode: payload bytes 0..)
+    // Window 0's stream words (decode: the wire; encode: payload bytes 0..),
+    // made from the raw aligned words dr: x0[0..3] (decode: header and nonce)
+    // for the header checks, the others behind window 0's keystream, where
+    // they are first needed and first waited for.
+    uint32_t x0[16];
+    uint32_t dr[17], sh0 = 0; // decode: raw words 0..16; encode: 0..8; the start's byte in its word
+    uint64_t ncv = 0;         // encode: the caller's nonce
+    unsigned long long psn = 0; // decode: the session's peer nonce before the batch
+    uint32_t dg = 0;            // encode: the session's downgrade_sub
+    uint32_t w_epoch = 0;       // without the relay: the wave's own reads of the call state
+    uint64_t w_nbase = 0;
     auto fetch = [&](uint32_t wgv) {
         i = wgv * kFramesBS + threadIdx.x;
         valid = i < nlim;
         ii = valid ? i : nlim - 1;
-        sid_ok = sid[ii] < max_sessions;
-        s = sid_ok ? sid[ii] : 0u; // (a frame of an unknown session is not processed)
+        // group A (at its head the wave's own reads of the call state: vector
+        // loads of one address, counted with the descriptors' -- a scalar
+        // load would put its round trip into every wait for an argument)
+        if (!relay) {
+            w_epoch = __hip_atomic_load(&zs->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!DEC && ctl.nonce_ctr)
+                w_nbase = __hip_atomic_load(ctl.nonce_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        uint32_t sidv = sid[ii];
+        uint64_t ioff = in_off[ii], ooff = out_off[ii];
+        L_in = len[ii];
+        uint32_t mfl = 0;
+        if (!DEC) {
+            mfl = flags[ii];
+            if (!ctl.nonce_ctr)
+                ncv = nonce[ii];
+        }
+        // (group A is awaited whole -- it comes back together -- so that
+        // every later wait counts group B's loads alone)
+        asm volatile(""
+                     : "+v"(sidv), "+v"(ioff), "+v"(ooff), "+v"(L_in), "+v"(mfl), "+v"(ncv), "+v"(w_epoch),
+                       "+v"(w_nbase)::"memory");
+        // group B
+        sid_ok = sidv < max_sessions;
+        s = sid_ok ? sidv : 0u; // (a frame of an unknown session is not processed)
         const DevSession &ses = sessions[s];
 #pragma unroll
         for (int t = 0; t < 8; ++t)
             key[t] = DEC ? ses.dec_key[t] : ses.enc_key[t];
-        src = in + in_off[ii];
-        dst = out + out_off[ii];
-        L_in = len[ii];
-        over = frame_over<DEC>(ctl, L_in, out_off[ii]); // the caller's bounds broken
+        src = in + ioff;
+        dst = out + ooff;
+        over = frame_over<DEC>(ctl, L_in, ooff); // the caller's bounds broken
         if (!DEC) {
-            hl = plaintext_header(flags[ii], ses.downgrade_sub, hw);
+            dg = ses.downgrade_sub;
+            // payload bytes 0 .. min(31, L_in - 1): the aligned words covering
+            // them (load_bytes_c<32>, load_window)
+            sh0 = (uint32_t) (uintptr_t) src & 3u;
+            if (L_in >= 32u) // two dwordx4 (and a dword when unaligned)
+                load_bytes_raw<32>(src, dr);
+            else // only words that hold a payload byte (at most nine)
+                load_window_raw<9>((const uint32_t *) (src - sh0), sh0, (int) L_in, dr);
+            asm volatile("" ::: "memory");
+            hl = plaintext_header(mfl, dg, hw);
             S = sid_ok && !over ? 32u + hl + L_in : 0u;
             A = (uint64_t) (uintptr_t) src - 32u - hl;
             B = (uint64_t) (uintptr_t) dst;
-            if (L_in >= 32u) { // payload bytes 0..31: two dwordx4 (and a dword when unaligned)
-                load_bytes_c<32>(src, x0);
-#pragma unroll
-                for (int k = 8; k < 16; ++k)
-                    x0[k] = 0;
-            } else {
-                load_window(src, (int) L_in, x0);
-            }
         } else {
             // the wire frame's first window: header, nonce, tag, 32 ciphertext bytes
             A = (uint64_t) (uintptr_t) src;
-            uint32_t d[17];
-            frame_load_raw(A, 0, L_in, d);
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                x0[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], (uint32_t) A & 3u);
+            sh0 = (uint32_t) A & 3u;
+            frame_load_raw(A, 0, L_in, dr);
+            psn = rp.peer[s];
+            asm volatile("" ::: "memory");
             B = (uint64_t) (uintptr_t) dst - 33u;
         }
     };
-    // the call state (see call_state_begin): thread 0's reads go out first,
-    // the frame's loads behind them, and the reads are waited for (to publish
-    // them in LDS) only after both are in flight
+    // The call state (see call_state_begin).  Without the relay, each wave's
+    // own reads at the head of group A; they pass through the statement
+    // behind the frame's loads, so they have been made when the wave reaches
+    // step 0's barrier, behind which thread 0 counts the workgroup.  With the
+    // relay, thread 0's reads go out first, the frame's loads behind them,
+    // and the barrier that hands them to the workgroup follows.
+    // (The two paths are kept apart to the end of the relay: where they share
+    // code between thread 0's reads and the barrier, the wait for a register
+    // those reads may still be writing lands in the other path's set-up.)
     CallState c0{};
-    if (threadIdx.x == 0) {
-        c0.epoch = __hip_atomic_load(&zs->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        c0.ticket = use_ticket ? atomicAdd(&zs->ticket, 1u) : 0u;
-        c0.nbase = DEC ? 0ull : nonce_base(ctl);
-    }
-    if (!use_ticket)
+    if (!relay) {
         fetch(blockIdx.x);
-    if (threadIdx.x == 0)
-        sh_cs = c0;
-    __syncthreads();
-    const CallState cs = sh_cs;
+        SEQ_STAMP(22u);
+        uint32_t e = __builtin_amdgcn_readfirstlane(w_epoch);
+        uint32_t b0 = __builtin_amdgcn_readfirstlane((uint32_t) w_nbase);
+        uint32_t b1 = __builtin_amdgcn_readfirstlane((uint32_t) (w_nbase >> 32));
+        asm volatile("" : "+s"(e), "+s"(b0), "+s"(b1));
+        c0.epoch = e;
+        c0.nbase = ((uint64_t) b1 << 32) | b0;
+    } else {
+        if (threadIdx.x == 0) {
+            c0.epoch = __hip_atomic_load(&zs->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            c0.ticket = use_ticket ? atomicAdd(&zs->ticket, 1u) : 0u;
+            c0.nbase = DEC ? 0ull : nonce_base(ctl);
+        }
+        if (!use_ticket)
+            fetch(blockIdx.x);
+        if (threadIdx.x == 0)
+            sh_cs = c0;
+        __syncthreads();
+        c0 = sh_cs;
+        if (use_ticket)
+            fetch(c0.ticket);
+    }
+    const CallState cs = c0;
     const uint32_t epoch = cs.epoch;
     const uint32_t wg = use_ticket ? cs.ticket : blockIdx.x;
-    if (use_ticket)
-        fetch(wg);
     const uint64_t nbase = cs.nbase;
     unsigned long long *const list_ctr = zs->list_ctr + (epoch & 1u);
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        zs->list_ctr[(epoch & 1u) ^ 1u] = 0;
 
     if (!DEC) {
-        const uint64_t nc = frame_nonce(nonce, ctl, nbase, ii);
+        const uint64_t nc = ctl.nonce_ctr ? nbase + ii : ncv; // (frame_nonce)
         n0 = bswap32((uint32_t) (nc >> 32));
         n1 = bswap32((uint32_t) nc);
     } else {
-        if (L_in < 64u)
-            mask_tail(x0, (int) L_in);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            x0[k] = __builtin_amdgcn_alignbyte(dr[k + 1], dr[k], sh0);
+        if (L_in < 16u) { // (words 4.. are masked where they are made, in step 0)
+            uint32_t t[16] = {x0[0], x0[1], x0[2], x0[3]};
+            mask_tail(t, (int) L_in);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                x0[k] = t[k];
+        }
         // mechanism_base.cpp:14-25, curve_mechanism_base.cpp:80-97
         const uint32_t b0 = x0[0] & 0xffu;
         if (L_in <= 1u || L_in <= b0)
@@ -1240,40 +1362,43 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         n1 = x0[3];
         S = status == 0 ? L_in : 0u;
     }
+#if ZMQG_SEQ_STAMPS
+    asm volatile("" : "+v"(S), "+v"(n0), "+v"(n1)); // (the stamp behind the header checks)
+#endif
+    SEQ_STAMP(23u);
     const bool small = valid && S <= max_stream;
-    unsigned long long vn = 0, wexcl = 0, psn = 0, wagg = 0;
+    unsigned long long vn = 0, wexcl = 0, wagg = 0;
     if (DEC) {
         vn = valid && status == 0 ? (((unsigned long long) bswap32(n0) << 32) | bswap32(n1)) : 0ull;
-        psn = rp.peer[s];
         if (valid && !lb) { // (several sessions: the replay tables' input)
             rp.vout[i] = vn;
             rp.psnap[i] = psn;
             if (rp.iota)
                 rp.iota[i] = i;
         }
-        if (lb) {
-            const unsigned long long sc = wave_scan_max_u64(vn);
-            const unsigned long long up = wave_prev_u64(sc);
-            if (lane == 63)
-                sh_wmax[threadIdx.x >> 6] = sc;
-            __syncthreads();
-            const uint32_t wv = threadIdx.x >> 6;
-            for (uint32_t k = 0; k < kFramesWaves; ++k) {
-                if (k < wv)
-                    wexcl = sh_wmax[k] > wexcl ? sh_wmax[k] : wexcl;
-                wagg = sh_wmax[k] > wagg ? sh_wmax[k] : wagg;
-            }
-            if (lane > 0)
-                wexcl = up > wexcl ? up : wexcl;
-            if (threadIdx.x == 0) {
-                if (use_rec) { // two relaxed stores, no wait between them or for the loads in flight
-                    __hip_atomic_store(rp.lb_rec + 2u * wg, lbrec_pack(epoch, (uint32_t) wagg), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(rp.lb_rec + 2u * wg + 1u, lbrec_pack(epoch, (uint32_t) (wagg >> 32)),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    lookback_publish(rp.lb_flag + wg, rp.lb_agg + wg, wagg, epoch, 1);
-                }
+    }
+    if (lb) {
+        const unsigned long long sc = wave_scan_max_u64(vn);
+        const unsigned long long up = wave_prev_u64(sc);
+        if (lane == 63)
+            sh_wmax[threadIdx.x >> 6] = sc;
+        __syncthreads();
+        const uint32_t wv = threadIdx.x >> 6;
+        for (uint32_t k = 0; k < kFramesWaves; ++k) {
+            if (k < wv)
+                wexcl = sh_wmax[k] > wexcl ? sh_wmax[k] : wexcl;
+            wagg = sh_wmax[k] > wagg ? sh_wmax[k] : wagg;
+        }
+        if (lane > 0)
+            wexcl = up > wexcl ? up : wexcl;
+        if (threadIdx.x == 0) {
+            if (use_rec) { // two relaxed stores, no wait between them or for the loads in flight
+                __hip_atomic_store(rp.lb_rec + 2u * wg, lbrec_pack(epoch, (uint32_t) wagg), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(rp.lb_rec + 2u * wg + 1u, lbrec_pack(epoch, (uint32_t) (wagg >> 32)),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+                lookback_publish(rp.lb_flag + wg, rp.lb_agg + wg, wagg, epoch, 1);
             }
         }
     }
@@ -1368,6 +1493,14 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
                        "s"(sq_m[2]), "s"(sq_m[3]), "s"(sq_m[4])
                      : "memory", "scc");
     };
+    // (The compiler does not count the moves of sq_dma: a counted wait behind
+    // them would wait for them too.  What window 0's keystream reads has
+    // arrived here -- the key is named, the nonce was checked above -- and the
+    // next wait, for window 0's other words, comes a keystream later.)
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+        asm volatile("" : "+v"(key[t]));
+    asm volatile("" : "+v"(n0), "+v"(n1));
     if (steps > 1u)
         sq_dma(1u);
 
@@ -1432,6 +1565,40 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
     {
         uint32_t ks[16];
         salsa20_block(ks, key, n0, n1, 0, 0);
+        // (the keystream is pinned ahead of the barrier and of the wait for
+        // window 0's other words, as in the steps)
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            asm volatile("" : "+v"(ks[k]));
+        SEQ_STAMP(24u);
+        if (!relay)
+            __syncthreads(); // (every wave has its call state: thread 0 may count the workgroup, below)
+        // window 0's words behind the header and the nonce: their first use
+#pragma unroll
+        for (int k = DEC ? 5 : 0; k < (DEC ? 17 : 9); ++k)
+            asm volatile("" : "+v"(dr[k]));
+        // (a register kept to here: a SUBSCRIBE or CANCEL frame alone waits
+        // for it earlier; reused before window 0, it is waited for -- and
+        // group B with it -- ahead of the set-up)
+        if (!DEC)
+            asm volatile("" : "+v"(dg));
+        if (DEC) {
+#pragma unroll
+            for (int k = 4; k < 16; ++k)
+                x0[k] = __builtin_amdgcn_alignbyte(dr[k + 1], dr[k], sh0);
+            if (L_in < 64u)
+                mask_tail(x0, (int) L_in);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                x0[k] = __builtin_amdgcn_alignbyte(dr[k + 1], dr[k], sh0);
+#pragma unroll
+            for (int k = 8; k < 16; ++k)
+                x0[k] = 0;
+            if (L_in < 32u)
+                mask_tail(x0, (int) L_in);
+        }
+        SEQ_STAMP(63u);
         pk = poly32_key(ks[0], ks[1], ks[2], ks[3]);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -1514,7 +1681,7 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         }
     }
     SEQ_STAMP(2u);
-    call_state_count(zs);
+    call_state_count(zs); // (behind a barrier that every wave passed with its call state: the relay's, or step 0's)
 
     // ---- steps 1 ..: window t (its covers moved into LDS buffer t & 1 by
     // the previous step).  UNI: a uniform step (above), the same body with
@@ -1810,6 +1977,11 @@ __device__ __forceinline__ void frames_seq_impl(ZMQG_FRAMES_PARAMS)
         }
         big(i, list_ctr, nbase);
     }
+    // the next call's big-frame list (the previous body has finished with
+    // it); here and not at the start, where the registers of a store in
+    // flight are waited for -- group B with them -- when the set-up reuses them
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        zs->list_ctr[(epoch & 1u) ^ 1u] = 0;
     call_state_end<DEC>(zs, ctl, cs, n);
     frame_result_copy<DEC>(big);
     SEQ_STAMP(61u);

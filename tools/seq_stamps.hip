@@ -5,6 +5,11 @@
 // (24+t), at the end of the loop (60) and of the kernel (61); for steps 1..7
 // also when the window's input words are in registers (44+t), when the next
 // window's DMA has been issued (52+t) and when the stores have (36+t).
+// The phase before window 0 in its parts: the kernel's first instruction
+// (20), every line of its arguments there (21), group B issued (22), the
+// header checked (23; the stamped build pins S and the nonce there, the
+// product build does not, so the split around it is the stamped kernel's);
+// in window 0, its keystream done (24) and its other words there (63).
 // STAMP_REPS launches per direction back to back (the clock settles), the
 // last one stamped.  Prints one JSON line of medians over the waves, in
 // s_memtime ticks.
@@ -128,9 +133,17 @@ int main(int argc, char **argv)
             return v[v.size() / 2];
         };
         printf(", \"%s\": {\"total\": %lld, \"entry_to_window0\": %lld, \"window0\": %lld, \"window0_to_step1\": %lld, "
-               "\"steps_2_15_mean\": %.1f, \"step16\": %lld, \"loop_end_to_exit\": %lld, \"steps\": [",
+               "\"steps_2_15_mean\": %.1f, \"step16\": %lld, \"loop_end_to_exit\": %lld, ",
                dec ? "decode" : "encode", med(0, 61), med(0, 1), med(1, 2), med(2, 4), med(5, 19) / 14.0, med(19, 60),
                med(60, 61));
+        // the phase before window 0 in its parts: the kernel arguments (the
+        // first instruction to all of their lines there), group A (to group
+        // B issued), group B's head (to the header checks done), the set-up;
+        // then window 0's keystream and the wait for window 0's other words
+        printf("\"first_instruction_to_window0\": %lld, \"entry_parts\": {\"kernel_arguments\": %lld, "
+               "\"arguments_to_first_stamp\": %lld, \"group_a\": %lld, \"group_b_head\": %lld, "
+               "\"setup\": %lld, \"keystream0\": %lld, \"barrier_and_words\": %lld}, \"steps\": [",
+               med(20, 1), med(20, 21), med(21, 0), med(0, 22), med(22, 23), med(23, 1), med(1, 24), med(24, 63));
         for (int t = 1; t <= 7; ++t)
             printf("%s{\"t\": %d, \"compute_before_wait\": %lld, \"wait_to_input_ready\": %lld, \"xor_dma_issue\": %lld, "
                    "\"store_issue\": %lld, \"step\": %lld}",
