@@ -459,7 +459,21 @@ int zmqg_notify_quiesce(zmqg_ctx *ctx);
  * on hold empty frames: length 0, a malformed status); `out` at least
  * in_bytes.  Returns after the stream has synchronised: the result is the
  * call's only read back (the frame count stays on the device; the decode
- * runs over max_frames).  in_bytes < 2^31.
+ * runs over max_frames).  in_bytes < 2^31; any byte alignment of `in` is valid
+ * (the scan cuts the stream in 16-byte-aligned address space and reads no byte
+ * outside [in, in + in_bytes)).
+ * Early stop: a call may return fewer frames than are complete in the buffer,
+ * with error == 0, frames < max_frames, consumed < in_bytes and every status
+ * as the mechanism gives it (0 for valid frames).  It happens when the seven
+ * bytes in front of a short MESSAGE frame (the end of the previous frame's
+ * body, which the peer chooses) read as a LARGE header whose size field, completed by the frame's own flags
+ * and size bytes, passes max_msg_size and fits the buffer (for instance a
+ * flags byte with the LARGE bit and six zero bytes: the size is then the
+ * frame's own): the parse then ends with that frame as the call's last.  The
+ * returned frames are always a prefix of the reference decoder's, so the
+ * caller repeats the call from `consumed` (in + consumed, in_bytes - consumed)
+ * until a call returns 0 frames; only then are the bytes left an incomplete
+ * frame that waits for the socket.
  *
  * zmqg_decode_zmtp_async: the same, without synchronising: `result` must be
  * device-accessible (device memory, or pinned host memory from
@@ -470,7 +484,9 @@ int zmqg_notify_quiesce(zmqg_ctx *ctx);
  * maxmsgsize :74-84) over the receive buffers of many connections in one
  * asynchronous call -- an I/O thread's shape: n_streams buffers of at most
  * in_batch_size bytes each (src/options.cpp:221) -- with the semantics of
- * n_streams zmqg_decode_zmtp calls in stream order.  Stream s is
+ * n_streams zmqg_decode_zmtp calls in stream order, with one exception: this
+ * call's sequential parser has no early stop (see zmqg_decode_zmtp), it
+ * returns every complete frame of a stream up to max_frames.  Stream s is
  * in[stream_off[s] .. +stream_len[s]), received on session stream_sid[s];
  * streams do not overlap, any byte alignment of stream_off is valid,
  * stream_len[s] < 2^31, and no byte outside a stream is read (nothing

@@ -187,15 +187,31 @@ __device__ __forceinline__ uint64_t zmtp_block_excl4(uint64_t v, uint64_t &total
 // t0 = 16 KiB x tile, k = 0..3: consecutive lanes read consecutive chunks
 // (coalesced), each with the 16 bytes before it (a header) and the 8 after (a
 // signature's tail), so the signature and header tests run on registers.
+// `b` may have any byte alignment: tiles and chunks are cut in 16-byte-aligned
+// address space, as k_zmtp_streams cuts its tiles.  With mis = b's address
+// modulo 16 the stream is [mis, mis + n) there, a chunk's stream offset is its
+// aligned offset less mis (negative for the first chunk when mis > 0), the
+// vector loads are aligned, and no byte outside the stream is read.
 constexpr uint32_t kZmtpRounds = kZmtpWgBytes / 16u / kZmtpThreads; // 4
+__device__ __forceinline__ uint32_t zmtp_mis(const uint8_t *b)
+{
+    return (uint32_t) ((uintptr_t) b & 15u);
+}
+// tiles of the stream [b, b + n): what the host launches and reserves for
+__host__ __device__ __forceinline__ uint64_t zmtp_tiles(const uint8_t *b, uint64_t n)
+{
+    return (((uintptr_t) b & 15u) + n + kZmtpWgBytes - 1) / kZmtpWgBytes;
+}
 __device__ __forceinline__ void zmtp_scan_load(const uint8_t *b, uint64_t n, uint64_t tile,
                                                uint32_t (&w)[kZmtpRounds][10])
 {
     const uint64_t wg0 = tile * kZmtpWgBytes;
+    const uint32_t mis = zmtp_mis(b);
 #pragma unroll
     for (uint32_t k = 0; k < kZmtpRounds; ++k) {
-        const uint64_t base = wg0 + 16ull * (k * kZmtpThreads + threadIdx.x);
-        if (base >= 16 && base + 24 <= n) {
+        const uint64_t ub = wg0 + 16ull * (k * kZmtpThreads + threadIdx.x); // (aligned address space)
+        const int64_t base = (int64_t) ub - mis;
+        if (ub >= 16u + mis && ub + 24 <= mis + n) {
             const uint4 v0 = *(const uint4 *) (b + base - 16);
             const uint4 v1 = *(const uint4 *) (b + base);
             const uint2 v2 = *(const uint2 *) (b + base + 16);
@@ -214,7 +230,7 @@ __device__ __forceinline__ void zmtp_scan_load(const uint8_t *b, uint64_t n, uin
             for (int q = 0; q < 10; ++q) {
                 uint32_t x = 0;
                 for (int j = 0; j < 4; ++j) {
-                    const int64_t p = (int64_t) base - 16 + 4 * q + j;
+                    const int64_t p = base - 16 + 4 * q + j;
                     x |= (uint32_t) (p >= 0 && (uint64_t) p < n ? b[p] : 0u) << (8 * j);
                 }
                 w[k][q] = x;
@@ -226,19 +242,20 @@ __device__ __forceinline__ void zmtp_scan_load(const uint8_t *b, uint64_t n, uin
 // One tile's candidates from its registers: written in (k, thread) order,
 // which is stream order, after one block scan of the four rounds' counts
 // packed in 16-bit fields (a tile holds at most kZmtpWgCap = 2048 of them).
-__device__ __forceinline__ void zmtp_scan_tile(uint64_t n, int64_t max_msg, uint64_t tile,
+__device__ __forceinline__ void zmtp_scan_tile(uint64_t n, int64_t max_msg, uint64_t tile, uint32_t mis_b,
                                                const uint32_t (&w)[kZmtpRounds][10], uint64_t *cand_wg,
                                                uint64_t *count_wg, uint16_t *count16)
 {
     constexpr uint32_t R = kZmtpRounds;
     static_assert(R == 4, "four 16-bit count fields");
     const uint64_t wg0 = tile * kZmtpWgBytes;
+    const int64_t mis = mis_b; // (the chunk's stream offset: negative only for chunk 0 of a misaligned stream)
     uint64_t *const dst0 = cand_wg + (size_t) tile * kZmtpWgCap;
     uint64_t f[R][2]; // (at most 2 per chunk: signatures are >= 8 bytes apart)
     uint32_t cnt[R];
 #pragma unroll
     for (uint32_t k = 0; k < R; ++k) {
-        const uint64_t base = wg0 + 16ull * (k * kZmtpThreads + threadIdx.x);
+        const int64_t base = (int64_t) (wg0 + 16ull * (k * kZmtpThreads + threadIdx.x)) - mis;
         uint64_t f0 = 0, f1 = 0;
         uint32_t c = 0;
         auto at = [&](uint64_t p) { // (registers only: no dynamically indexed array)
@@ -251,8 +268,9 @@ __device__ __forceinline__ void zmtp_scan_tile(uint64_t n, int64_t max_msg, uint
         const uint32_t(&wk)[10] = w[k];
 #define ZMTP_SIG(Q, J)                                                                                           \
     if (__builtin_amdgcn_alignbyte(wk[5 + Q], wk[4 + Q], J) == 0x53454d07u &&                                    \
-        __builtin_amdgcn_alignbyte(wk[6 + Q], wk[5 + Q], J) == 0x45474153u && base + 4 * Q + J + 8 <= n)         \
-        at(zmtp_cand_at<16 + 4 * Q + J>(wk, base + 4 * Q + J, n, max_msg));
+        __builtin_amdgcn_alignbyte(wk[6 + Q], wk[5 + Q], J) == 0x45474153u && base + 4 * Q + J >= 0 &&           \
+        (uint64_t) (base + 4 * Q + J) + 8 <= n)                                                                  \
+        at(zmtp_cand_at<16 + 4 * Q + J>(wk, (uint64_t) (base + 4 * Q + J), n, max_msg));
 #define ZMTP_WORD(Q)                                                                                             \
     {                                                                                                            \
         const uint32_t x = wk[4 + Q] ^ 0x07070707u;                                                              \
@@ -302,7 +320,7 @@ __global__ __launch_bounds__(kZmtpThreads) void k_zmtp_scan(const uint8_t *b, ui
 {
     uint32_t w[kZmtpRounds][10];
     zmtp_scan_load(b, n, blockIdx.x, w);
-    zmtp_scan_tile(n, max_msg, blockIdx.x, w, cand_wg, count_wg, count16);
+    zmtp_scan_tile(n, max_msg, blockIdx.x, zmtp_mis(b), w, cand_wg, count_wg, count16);
 }
 
 // The same as a persistent grid: each workgroup takes tiles blockIdx.x,
@@ -321,7 +339,7 @@ __global__ __launch_bounds__(kZmtpThreads) void k_zmtp_scan_p(const uint8_t *b, 
         const uint64_t tn = t + gridDim.x;
         if (tn < nwg)
             zmtp_scan_load(b, n, tn, wb);
-        zmtp_scan_tile(n, max_msg, t, wa, cand_wg, count_wg, count16);
+        zmtp_scan_tile(n, max_msg, t, zmtp_mis(b), wa, cand_wg, count_wg, count16);
         if (tn >= nwg)
             break;
         __syncthreads(); // (the block scan's LDS is reused)
@@ -329,7 +347,7 @@ __global__ __launch_bounds__(kZmtpThreads) void k_zmtp_scan_p(const uint8_t *b, 
         const uint64_t tn2 = t + gridDim.x;
         if (tn2 < nwg)
             zmtp_scan_load(b, n, tn2, wa);
-        zmtp_scan_tile(n, max_msg, t, wb, cand_wg, count_wg, count16);
+        zmtp_scan_tile(n, max_msg, t, zmtp_mis(b), wb, cand_wg, count_wg, count16);
         if (tn2 >= nwg)
             break;
         __syncthreads();

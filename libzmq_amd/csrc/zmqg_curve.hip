@@ -3225,7 +3225,7 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
     std::lock_guard<std::mutex> lk(ctx->mu);
     ZmtpWs &z = ctx->zw;
     int rc;
-    const uint64_t nwg = (in_bytes + kZmtpWgBytes - 1) / kZmtpWgBytes;
+    const uint64_t nwg = zmtp_tiles(in, in_bytes); // (cut in aligned address space: `in` has any alignment)
     if (nwg > z.g_cap) {
         const uint64_t cap = grown_cap(z.g_cap, 64, nwg);
         z.g_cap = 0;

@@ -102,6 +102,7 @@ _lib.zmqg_decode_zmtp_async.argtypes = [_P, _U32, _P, _U64, ctypes.c_int64, _U64
 _lib.zmqg_decode_zmtp_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int64, _U64] + [_P] * 8
 _lib.zmqg_encode_zmtp_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 7 + [_U64] + [_P] * 4
 ZMTP_MULTI_TILE = 16384  # kZmtpMultiTile: bytes of a stream zmqg_decode_zmtp_multi's kernel holds in LDS at a time
+ZMTP_SCAN_TILE = 16384  # kZmtpWgBytes: bytes of a stream one workgroup of zmqg_decode_zmtp's candidate scan lists
 
 
 class ForwardResult(ctypes.Structure):  # zmqg_forward_result
