@@ -50,6 +50,9 @@
  *     src/xpub.cpp:290-326,
  *     src/generic_mtrie_impl.hpp:523-561,
  *     src/dist.cpp:49-62                             zmqg_forward_zmtp_sub_multi
+ *   xpub_t::xread_activated / mtrie add, rm / xpipe_terminated
+ *     src/xpub.cpp:72-170, :253-277,
+ *     src/generic_mtrie_impl.hpp:41-126, 376-521     zmqg_subs_update_multi
  *   router_t::xrecv / xsend, lookup_out_pipe
  *     src/router.cpp:263-332, :161-261,
  *     src/socket_base.cpp:2187-2200                  zmqg_forward_zmtp_router_multi
@@ -822,7 +825,8 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
  * N == 0 the two are not queued.
  * Not offered: ROUTER identities (zmqg_forward_zmtp_router_multi, which does not
  * combine with this table); maintaining the table on the device from
- * SUBSCRIBE / CANCEL commands (they stay held commands for the host);
+ * SUBSCRIBE / CANCEL commands (they stay held commands for the host;
+ * zmqg_subs_update_multi, a call of its own, keeps such a table);
  * ZMQ_XPUB_MANUAL, ZMQ_XPUB_NODROP and high-water marks, the welcome message;
  * the XSUB upstream direction; WebSocket framing. */
 #define ZMQG_SUBS_INVERT 1u            /* options.invert_matching: dist_t::reverse_match, src/dist.cpp:64-78 */
@@ -838,6 +842,175 @@ typedef struct zmqg_forward_subs {
 } zmqg_forward_subs;
 int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
                                 const zmqg_forward_subs *subs, void *stream);
+
+/* zmqg_subs_update_multi: the subscription direction of an XSUB/XPUB proxy --
+ * the SUBSCRIBE / CANCEL traffic that zmqg_decode_zmtp_multi (or a forward
+ * call's receive side) has decoded from the subscribers' connections, applied
+ * to a subscription store that lives on the device, published as the table
+ * zmqg_forward_zmtp_sub_multi reads, and judged for what must be passed
+ * upstream: xpub_t::xread_activated (src/xpub.cpp:72-170) with
+ * generic_mtrie_t::add / rm (src/generic_mtrie_impl.hpp:41-126, 376-521), and
+ * xpub_t::xpipe_terminated (src/xpub.cpp:253-277) for peers that have gone.
+ * The call is asynchronous on `stream`; the host neither synchronises nor reads
+ * the store back.  Every array is device-accessible unless marked HOST; the two
+ * HOST arrays are copied before the call returns.
+ *
+ * The store.  Caller-owned device memory, all zero = empty, written by this
+ * call only: cnt[n_dst], slot_len[n_dst * cap], bytes[n_dst * cap * slot_bytes]
+ * (8-byte aligned).  Destination t's live prefixes are its slots t * cap + i,
+ * i < cnt[t]: prefix = bytes[(t * cap + i) * slot_bytes .. +slot_len[t * cap +
+ * i]).  Their order within a destination is unspecified (a removal moves the
+ * destination's last slot into the hole); nothing observable depends on it.
+ * The device never trusts the store: cnt[t] is read as min(cnt[t], cap),
+ * slot_len as min(slot_len, slot_bytes), and no byte outside the three arrays is
+ * read or written.  A store that only this call has written holds no prefix
+ * twice in one destination; for any other, "the destinations holding a topic"
+ * below counts slots, and a cancel removes the first slot that holds the topic.
+ * cnt[t] is written (clamped) for the destinations named in stream_dst and
+ * clear_dst, the others' entries are left as they are.
+ *
+ * The view.  sub_idx[n_dst + 1], sub_off[n_dst * cap], sub_len[n_dst * cap] are
+ * outputs: zmqg_forward_subs's arrays.  After the call sub_idx is the exclusive
+ * sum of the new counts, entry sub_idx[t] + i names slot t * cap + i -- sub_off
+ * (t * cap + i) * slot_bytes, sub_len the slot's length -- and entries at or
+ * past sub_idx[n_dst] are left as they were.  The forward call takes sub_bytes =
+ * bytes, sub_bytes_len = n_dst * cap * slot_bytes, n_subs = n_dst * cap.
+ *
+ * The input.  n_streams, max_frames, results, frame_len, plain_off, flags_out,
+ * status_out, plain are the outputs of a zmqg_decode_zmtp_multi call queued
+ * earlier on the same stream, with its slot numbering s * max_frames + j.
+ * stream_dst (HOST, n_streams entries): stream s edits destination
+ * stream_dst[s].  The elements of stream s are its slots j < min(results[s].
+ * frames, max_frames) in order, up to but not including the first one with a
+ * non-zero status (the connection fails there: nothing from that frame on is
+ * examined).
+ *
+ * Classification.  An element's payload p is the frame_len - 33 bytes at
+ * plain[plain_off]; what the engine and XPUB make of it
+ * (zmtp_engine_t::process_command_message, src/zmtp_engine.cpp:533-563, whose
+ * result is ignored at src/stream_engine_base.cpp:635-637;
+ * session_base_t::push_msg, src/session_base.cpp:158-172; msg_t::command_body,
+ * src/msg.cpp:526-559; src/xpub.cpp:88-100):
+ *   ZMQG_MSG_COMMAND set:  len >= 10 and p starts with "\x09SUBSCRIBE": a
+ *     subscribe, topic p[10..); len >= 7 and p starts with "\x06CANCEL": a
+ *     cancel, topic p[7..); anything else (PING, PONG, other commands, len 0, a
+ *     name length byte above len - 1) is no subscription element: the session
+ *     drops it or the host handles it, it is never an error.
+ *   ZMQG_MSG_COMMAND clear:  len >= 1 and p[0] 1 / 0: a subscribe / cancel,
+ *     topic p[1..) (what a downgrade_sub peer sends); anything else is an XPUB
+ *     user message, the host's to deal with, and no subscription element.
+ *   ZMQG_MSG_MORE is ignored (ZMQ_ONLY_FIRST_SUBSCRIBE off).
+ *
+ * Apply.  Each stream's subscription elements are applied to its destination
+ * in order; sub_status says what became of each:
+ *   ZMQG_SUB_NONE       no subscription element
+ *   ZMQG_SUB_ADDED      subscribe, stored
+ *   ZMQG_SUB_DUPLICATE  subscribe, the destination already holds exactly these bytes
+ *   ZMQG_SUB_REMOVED    cancel, removed
+ *   ZMQG_SUB_NOT_FOUND  cancel, the destination does not hold it (also a topic
+ *                       longer than slot_bytes)
+ *   ZMQG_SUB_FULL       subscribe, cnt == cap
+ *   ZMQG_SUB_TOO_LONG   subscribe, topic longer than slot_bytes
+ * FULL and TOO_LONG change nothing: they are the host's signal to deal with
+ * that subscriber.  The empty topic is an ordinary prefix.
+ *
+ * Clear.  clear_dst (HOST, n_clear entries) names destinations whose peer has
+ * gone.  Every prefix such a destination t holds is removed and cnt[t] becomes
+ * 0; for each former slot i < cnt_before: clear_len[t * cap + i] = its length,
+ * clear_note[t * cap + i] = its upstream verdict (0 / 1), and the prefix bytes
+ * and slot_len stay in the store until a later call reuses the slot.
+ * clear_cnt[k] = cnt_before of clear_dst[k].  Every other entry of clear_len
+ * and clear_note is left as it was.
+ *
+ * Upstream.  The order of events is the one of a replay: the clears in
+ * clear_dst order (a destination's slots in slot order), then the elements in
+ * (stream, slot) order.  With H = the destinations holding the topic just
+ * before an event in that order:
+ *   an ADDED notifies when H == 0 (mtrie add's first_added);
+ *   a REMOVED or cleared prefix notifies when H == 1 (last_value_removed);
+ *   a NOT_FOUND cancel notifies -- the reference's rule is rm_result !=
+ *     values_remain (src/xpub.cpp:118-122), which lets not_found through, and
+ *     that is kept;
+ *   DUPLICATE, FULL, TOO_LONG and NONE do not notify.
+ * ZMQG_SUBS_VERBOSE: every ADDED and DUPLICATE notifies (ZMQ_XPUB_VERBOSE).
+ * ZMQG_SUBS_VERBOSER: that, and every cancel and every cleared prefix
+ * (ZMQ_XPUB_VERBOSER).
+ *
+ * Per-slot outputs, n_streams * max_frames entries each, all written:
+ * sub_status; topic_off, an absolute offset into `plain`, and topic_len;
+ * note_flags, ZMQG_MSG_SUBSCRIBE or ZMQG_MSG_CANCEL for any subscription
+ * element; note_stream, 0 when the slot notifies, else UINT32_MAX.  A NONE slot
+ * gets 0 / 0 / 0 / 0 / UINT32_MAX.  topic_off, topic_len, note_flags and
+ * note_stream are zmqg_encode_zmtp_multi's in_off, len, flags and frame_stream
+ * with in = plain and one stream, the upstream session: one more queued call
+ * sends the notifications upstream, no read-back.  results_out[s]: seen (the
+ * stream's subscription elements), changed (ADDED + REMOVED), notes, rejected
+ * (FULL + TOO_LONG).
+ *
+ * Returns -EINVAL for a null ctx or args, args->size != sizeof(zmqg_subs_update),
+ * flag bits other than the two above, n_dst > 8192, cap == 0, slot_bytes no
+ * multiple of 8 or outside 8 .. 65536, n_dst * cap > 2^31 - 1, n_streams,
+ * max_frames or n_streams * max_frames > 2^31 - 1, a null sub_idx; with n_dst >
+ * 0 a null cnt, slot_len, bytes, sub_off or sub_len or a misaligned bytes; with
+ * n_streams > 0 a null stream_dst, results or results_out; with n_streams *
+ * max_frames > 0 a null input or per-slot array; with n_clear > 0 a null
+ * clear_dst, clear_cnt, clear_len or clear_note; entries of stream_dst or
+ * clear_dst that are not distinct or not below n_dst, or a destination named
+ * in both.  Nothing is queued then.  With n_streams == 0 and n_clear == 0 only
+ * the view is republished; max_frames == 0 is valid.
+ * Launches: five kernels and one copy whatever the sizes are (classify; the
+ * holders of every topic at call start; apply; the verdicts; the view); a
+ * kernel with nothing to do is not queued.  The verdicts compare every event
+ * with the events before it: the call is off the per-message path.
+ * Not offered: ZMQ_XPUB_MANUAL, ZMQ_ONLY_FIRST_SUBSCRIBE, the welcome message,
+ * fan-out of the notifications to several upstreams (one encode call per
+ * upstream), growing a store in place. */
+#define ZMQG_SUB_NONE 0
+#define ZMQG_SUB_ADDED 1
+#define ZMQG_SUB_DUPLICATE 2
+#define ZMQG_SUB_REMOVED 3
+#define ZMQG_SUB_NOT_FOUND 4
+#define ZMQG_SUB_FULL 5
+#define ZMQG_SUB_TOO_LONG 6
+#define ZMQG_SUBS_VERBOSE 2u           /* ZMQ_XPUB_VERBOSE: _verbose_subs, src/xpub.cpp:189-191 */
+#define ZMQG_SUBS_VERBOSER 4u          /* ZMQ_XPUB_VERBOSER: and _verbose_unsubs, src/xpub.cpp:192-194 */
+#define ZMQG_SUBS_MAX_DST 8192u
+typedef struct zmqg_subs_result {
+    uint64_t seen;                     /* subscription elements of the stream */
+    uint64_t changed;                  /* ADDED + REMOVED */
+    uint64_t notes;                    /* slots that notify */
+    uint64_t rejected;                 /* FULL + TOO_LONG */
+} zmqg_subs_result;
+typedef struct zmqg_subs_update {
+    uint32_t size, flags;              /* sizeof(zmqg_subs_update); ZMQG_SUBS_VERBOSE / _VERBOSER */
+    uint64_t n_dst, cap, slot_bytes;   /* the store */
+    uint32_t *cnt;
+    uint32_t *slot_len;
+    uint8_t *bytes;
+    uint32_t *sub_idx;                 /* the view */
+    uint64_t *sub_off;
+    uint32_t *sub_len;
+    uint64_t n_streams, max_frames;    /* the input: a zmqg_decode_zmtp_multi call's */
+    const zmqg_zmtp_result *results;
+    const uint32_t *frame_len;
+    const uint64_t *plain_off;
+    const uint8_t *flags_out;
+    const int32_t *status_out;
+    const uint8_t *plain;
+    const uint32_t *stream_dst;        /* HOST, n_streams */
+    uint64_t n_clear;                  /* destinations whose peer has gone */
+    const uint32_t *clear_dst;         /* HOST, n_clear */
+    uint32_t *clear_cnt;               /* n_clear */
+    uint32_t *clear_len;               /* n_dst * cap */
+    uint8_t *clear_note;               /* n_dst * cap */
+    int32_t *sub_status;               /* per slot, n_streams * max_frames each */
+    uint64_t *topic_off;
+    uint32_t *topic_len;
+    uint8_t *note_flags;
+    uint32_t *note_stream;
+    zmqg_subs_result *results_out;     /* n_streams */
+} zmqg_subs_update;
+int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *stream);
 
 /* zmqg_forward_zmtp_router_multi: zmqg_forward_zmtp_multi for a proxy with a
  * ROUTER side -- a request/reply broker, a worker pool.  What a ROUTER does to

@@ -101,6 +101,10 @@ struct ZmtpWs {
     DevBuf<uint32_t> e_head;    // [e_cap] the index in Q(s) of each forwarded element's head
     uint64_t v_cap = 0;         // zmqg_forward_zmtp_router_multi with ROUTE: elements
     DevBuf<uint32_t> e_verdict; // [v_cap] at a head: the destination its address names, or UNKNOWN / MALFORMED
+    uint64_t u_cap = 0;         // zmqg_subs_update_multi: events (cleared slots, then the decode call's slots)
+    DevBuf<uint32_t> u_h0;      // [u_cap] the slots holding the event's topic at call start
+    DevBuf<int8_t> u_delta;     // [u_cap] what the event did to its destination's hold on the topic: +1 / -1 / 0
+    DevBuf<uint32_t> u_tab;     // the call's host arrays: stream_dst, clear_dst
 };
 } // namespace
 

@@ -61,6 +61,7 @@
 #include "curve_forward.hpp"
 #include "curve_fwd_match.hpp"
 #include "curve_fwd_route.hpp"
+#include "curve_subs.hpp"
 #include "curve_ws.hpp"
 
 using namespace zmqg;
@@ -3607,6 +3608,109 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
          (router->id_bytes_len > 0 && !router->id_bytes)))
         return -EINVAL;
     return forward_multi_impl(ctx, args, nullptr, router->flags ? router : nullptr, stream);
+}
+
+// The launch-free checks, the two host arrays through the pinned staging, then
+// curve_subs.hpp's five kernels back to back on `stream` under one hold of
+// ctx->mu; a kernel without a wave to run is not queued.
+int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *stream)
+{
+    static_assert(kSubNone == ZMQG_SUB_NONE && kSubAdded == ZMQG_SUB_ADDED && kSubDuplicate == ZMQG_SUB_DUPLICATE &&
+                      kSubRemoved == ZMQG_SUB_REMOVED && kSubNotFound == ZMQG_SUB_NOT_FOUND &&
+                      kSubFull == ZMQG_SUB_FULL && kSubTooLong == ZMQG_SUB_TOO_LONG &&
+                      kSubsVerbose == ZMQG_SUBS_VERBOSE && kSubsVerboser == ZMQG_SUBS_VERBOSER &&
+                      kSubsMsgCommand == ZMQG_MSG_COMMAND && kSubsMsgSubscribe == ZMQG_MSG_SUBSCRIBE &&
+                      kSubsMsgCancel == ZMQG_MSG_CANCEL && sizeof(SubsResult) == sizeof(zmqg_subs_result),
+                  "curve_subs.hpp restates the header's values");
+    if (!ctx || !args || args->size != sizeof *args || (args->flags & ~(ZMQG_SUBS_VERBOSE | ZMQG_SUBS_VERBOSER)) != 0)
+        return -EINVAL;
+    const zmqg_subs_update &a = *args;
+    const uint64_t D = a.n_dst, S = a.n_streams, MF = a.max_frames, C = a.n_clear;
+    if (D > ZMQG_SUBS_MAX_DST || a.cap == 0 || a.cap > 0x7fffffffull || a.slot_bytes < 8 || a.slot_bytes > 65536 ||
+        (a.slot_bytes & 7u) || check_n(D * a.cap))
+        return -EINVAL;
+    if (check_n(S) || check_n(MF) || check_n(S * MF) || C > D || !a.sub_idx)
+        return -EINVAL;
+    if (D > 0 && (!a.cnt || !a.slot_len || !a.bytes || ((uintptr_t) a.bytes & 7u) || !a.sub_off || !a.sub_len))
+        return -EINVAL;
+    if (S > 0 && (!a.stream_dst || !a.results || !a.results_out))
+        return -EINVAL;
+    if (S * MF > 0 && (!a.frame_len || !a.plain_off || !a.flags_out || !a.status_out || !a.plain || !a.sub_status ||
+                       !a.topic_off || !a.topic_len || !a.note_flags || !a.note_stream))
+        return -EINVAL;
+    if (C > 0 && (!a.clear_dst || !a.clear_cnt || !a.clear_len || !a.clear_note))
+        return -EINVAL;
+    {
+        std::vector<uint8_t> named(D, 0); // no destination twice: one wave edits it
+        for (uint64_t i = 0; i < S + C; ++i) {
+            const uint32_t t = i < S ? a.stream_dst[i] : a.clear_dst[i - S];
+            if (t >= D || named[t])
+                return -EINVAL;
+            named[t] = 1;
+        }
+    }
+    hipStream_t st = (hipStream_t) stream;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ZmtpWs &z = ctx->zw;
+    int rc;
+    if ((rc = order_after_last(ctx, st)))
+        return rc;
+    const SubsStore store{D, a.cap, a.slot_bytes, a.cnt, a.slot_len, a.bytes};
+    const uint64_t EC = C * a.cap, E = EC + S * MF, per = kSubsThreads / 64u; // (E < 2^32)
+    const uint32_t *d_sdst = nullptr, *d_cdst = nullptr;
+    if (S + C > 0) {
+        if ((rc = sinst_room(ctx, 4 * (size_t) (S + C))))
+            return rc;
+        if (S)
+            memcpy(ctx->sinst, a.stream_dst, 4 * (size_t) S);
+        if (C)
+            memcpy(ctx->sinst + 4 * (size_t) S, a.clear_dst, 4 * (size_t) C);
+        ZRESERVE(ctx, z.u_tab, grown_cap(z.u_tab.count, 1024, S + C), st);
+        ZCHECK(ctx, hipMemcpyAsync(z.u_tab, ctx->sinst, 4 * (size_t) (S + C), hipMemcpyHostToDevice, st));
+        ZCHECK(ctx, hipEventRecord(ctx->sinst_done, st));
+        d_sdst = z.u_tab;
+        d_cdst = d_sdst + S;
+    }
+    if (E > z.u_cap) {
+        const uint64_t cap = grown_cap(z.u_cap, 1024, E);
+        z.u_cap = 0;
+        ZRESERVE(ctx, z.u_h0, cap, st);
+        ZRESERVE(ctx, z.u_delta, cap, st);
+        z.u_cap = cap;
+    }
+    if (S * MF > 0) {
+        hipLaunchKernelGGL(k_subs_classify, dim3((unsigned) ((S + per - 1) / per)), dim3(kSubsThreads), 0, st,
+                           (uint32_t) S, MF, a.results, a.frame_len, a.plain_off, a.flags_out, a.status_out, a.plain,
+                           a.sub_status, a.topic_off, a.topic_len, a.note_flags, a.note_stream, z.u_delta.p + EC);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    if (E > 0) {
+        const uint64_t gx = E < (1ull << 30) ? E : (1ull << 30); // (one workgroup per event; E < 2^32)
+        hipLaunchKernelGGL(k_subs_holders, dim3((unsigned) gx, (unsigned) ((E + gx - 1) / gx)), dim3(kSubsThreads), 0,
+                           st, E, EC, store, d_cdst, (const uint8_t *) a.note_flags, (const uint64_t *) a.topic_off,
+                           (const uint32_t *) a.topic_len, a.plain, z.u_h0.p);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    if (S + C > 0) {
+        hipLaunchKernelGGL(k_subs_apply, dim3((unsigned) ((S + C + per - 1) / per)), dim3(kSubsThreads), 0, st,
+                           (uint32_t) S, MF, (uint32_t) C, EC, store, d_sdst, d_cdst, (const uint8_t *) a.note_flags,
+                           (const uint64_t *) a.topic_off, (const uint32_t *) a.topic_len, a.plain, a.sub_status,
+                           z.u_delta.p, (SubsResult *) a.results_out, a.clear_cnt, a.clear_len);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    if (E > 0) {
+        hipLaunchKernelGGL(k_subs_resolve, dim3((unsigned) ((E + per - 1) / per)), dim3(kSubsThreads), 0, st, E, EC, MF,
+                           a.flags, store, d_cdst, (const uint32_t *) a.clear_cnt, (const uint8_t *) a.note_flags,
+                           (const uint64_t *) a.topic_off, (const uint32_t *) a.topic_len, a.plain,
+                           (const int32_t *) a.sub_status, (const int8_t *) z.u_delta.p, (const uint32_t *) z.u_h0.p,
+                           a.note_stream, a.clear_note, (SubsResult *) a.results_out);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_subs_publish, dim3((unsigned) (D ? D : 1)), dim3(kSubsThreads), 0, st, store, a.sub_idx,
+                       a.sub_off, a.sub_len);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
 }
 
 int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,

@@ -129,6 +129,29 @@ class ForwardSubs(ctypes.Structure):  # zmqg_forward_subs
                 ("sub_len", _P), ("sub_bytes", _P), ("sub_bytes_len", _U64), ("match_out", _P)]
 
 
+# ZMQG_SUB_*: what became of a slot of zmqg_subs_update_multi
+SUB_NONE, SUB_ADDED, SUB_DUPLICATE, SUB_REMOVED, SUB_NOT_FOUND, SUB_FULL, SUB_TOO_LONG = range(7)
+SUBS_VERBOSE, SUBS_VERBOSER = 2, 4  # ZMQG_SUBS_VERBOSE / _VERBOSER
+SUBS_MAX_DST = 8192  # ZMQG_SUBS_MAX_DST
+SUBS_NO_NOTE = 0xffffffff  # note_stream of a slot that does not notify
+
+
+class SubsResult(ctypes.Structure):  # zmqg_subs_result
+    _fields_ = [("seen", _U64), ("changed", _U64), ("notes", _U64), ("rejected", _U64)]
+
+
+class SubsUpdate(ctypes.Structure):  # zmqg_subs_update
+    _fields_ = [("size", _U32), ("flags", _U32), ("n_dst", _U64), ("cap", _U64), ("slot_bytes", _U64),
+                ("cnt", _P), ("slot_len", _P), ("bytes", _P), ("sub_idx", _P), ("sub_off", _P), ("sub_len", _P),
+                ("n_streams", _U64), ("max_frames", _U64), ("results", _P), ("frame_len", _P), ("plain_off", _P),
+                ("flags_out", _P), ("status_out", _P), ("plain", _P), ("stream_dst", _P),
+                ("n_clear", _U64), ("clear_dst", _P), ("clear_cnt", _P), ("clear_len", _P), ("clear_note", _P),
+                ("sub_status", _P), ("topic_off", _P), ("topic_len", _P), ("note_flags", _P), ("note_stream", _P),
+                ("results_out", _P)]
+
+
+_lib.zmqg_subs_update_multi.argtypes = [_P, ctypes.POINTER(SubsUpdate), _P]
+
 ROUTER_PREPEND, ROUTER_ROUTE = 1, 2  # ZMQG_ROUTER_*
 ROUTE_NONE, ROUTE_ADDRESS, ROUTE_UNKNOWN, ROUTE_MALFORMED = 0xffffffff, 0xfffffffe, 0xfffffffd, 0xfffffffc  # ZMQG_ROUTE_*
 
@@ -544,6 +567,90 @@ class CurveContext:
         lens = np.array([len(p) for p in flat], np.uint32)
         off = (np.cumsum(lens, dtype=np.uint64) - lens).astype(np.uint64)
         return idx, off, lens, np.frombuffer(b"".join(flat), np.uint8).copy()
+
+    @staticmethod
+    def subs_store(n_dst, cap, slot_bytes, device=None):
+        """An empty subscription store for subs_update_multi and its view, as a
+        dict of zeroed device tensors: cnt int32 [n_dst], slot_len int32
+        [n_dst * cap], bytes uint8 [n_dst * cap * slot_bytes] (the store);
+        sub_idx int32 [n_dst + 1], sub_off int64 and sub_len int32 [n_dst *
+        cap] (the view, forward_zmtp_sub_multi's table with sub_bytes =
+        bytes); plus n_dst, cap, slot_bytes."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        n = int(n_dst) * int(cap)
+        z = lambda count, dt: torch.zeros((max(int(count), 1),), dtype=dt, device=dev)
+        return dict(n_dst=int(n_dst), cap=int(cap), slot_bytes=int(slot_bytes), cnt=z(n_dst, torch.int32),
+                    slot_len=z(n, torch.int32), bytes=z(n * int(slot_bytes), torch.uint8),
+                    sub_idx=z(int(n_dst) + 1, torch.int32), sub_off=z(n, torch.int64), sub_len=z(n, torch.int32))
+
+    @staticmethod
+    def subs_store_view(store, view=False):
+        """The prefixes a store holds (synchronised), a list of bytes per
+        destination, read as the device reads it: counts clamped to cap,
+        lengths to slot_bytes.  view=True: the same through the published
+        view (sub_idx / sub_off / sub_len over bytes), as the forward call
+        reads it."""
+        host = lambda x: x if isinstance(x, np.ndarray) else x.cpu().numpy()
+        D, cap, sb = store["n_dst"], store["cap"], store["slot_bytes"]
+        raw = host(store["bytes"]).tobytes()
+        if view:
+            idx, off, ln = (host(store[k]).view(t) for k, t in (("sub_idx", np.uint32), ("sub_off", np.uint64),
+                                                                ("sub_len", np.uint32)))
+            return [[raw[int(off[j]):int(off[j]) + int(ln[j])] for j in range(int(idx[t]), int(idx[t + 1]))]
+                    for t in range(D)]
+        cnt, sl = host(store["cnt"]).view(np.uint32), host(store["slot_len"]).view(np.uint32)
+        return [[raw[(t * cap + i) * sb:(t * cap + i) * sb + min(int(sl[t * cap + i]), sb)]
+                 for i in range(min(int(cnt[t]), cap))] for t in range(D)]
+
+    @staticmethod
+    def _subs_args(store, stream_dst, max_frames, results, frame_len, plain_off, flags_out, status_out, plain,
+                   sub_status, topic_off, topic_len, note_flags, note_stream, results_out, clear_dst, clear_cnt,
+                   clear_len, clear_note, flags):
+        """The zmqg_subs_update of a subs_update_multi call, and the host arrays it points into."""
+        sd = np.ascontiguousarray([] if stream_dst is None else stream_dst, dtype=np.uint32)
+        cd = np.ascontiguousarray([] if clear_dst is None else clear_dst, dtype=np.uint32)
+        a = SubsUpdate(ctypes.sizeof(SubsUpdate), int(flags), store["n_dst"], store["cap"], store["slot_bytes"],
+                       _ptr(store["cnt"]), _ptr(store["slot_len"]), _ptr(store["bytes"]), _ptr(store["sub_idx"]),
+                       _ptr(store["sub_off"]), _ptr(store["sub_len"]), len(sd), int(max_frames), _ptr(results),
+                       _ptr(frame_len), _ptr(plain_off), _ptr(flags_out), _ptr(status_out), _ptr(plain),
+                       sd.ctypes.data if len(sd) else None, len(cd), cd.ctypes.data if len(cd) else None,
+                       _ptr(clear_cnt), _ptr(clear_len), _ptr(clear_note), _ptr(sub_status), _ptr(topic_off),
+                       _ptr(topic_len), _ptr(note_flags), _ptr(note_stream), _ptr(results_out))
+        return a, (sd, cd)
+
+    def subs_update_multi(self, store, stream_dst=None, max_frames=0, results=None, frame_len=None, plain_off=None,
+                          flags_out=None, status_out=None, plain=None, sub_status=None, topic_off=None,
+                          topic_len=None, note_flags=None, note_stream=None, results_out=None, clear_dst=None,
+                          clear_cnt=None, clear_len=None, clear_note=None, flags=0, stream=None):
+        """An XPUB's subscription direction in one asynchronous call
+        (zmqg_subs_update_multi): the SUBSCRIBE / CANCEL elements that a
+        decode_zmtp_multi call queued earlier on the stream has left in
+        results / frame_len / plain_off / flags_out / status_out / plain
+        (max_frames slots a stream) are applied to `store` (subs_store()),
+        stream s editing destination stream_dst[s]; the destinations in
+        clear_dst are emptied; the view is republished.  stream_dst and
+        clear_dst are host sequences, copied before the call returns.
+        Per slot (n_streams * max_frames entries): sub_status int32 (SUB_*),
+        topic_off int64, topic_len int32, note_flags uint8 (SUBSCRIBE /
+        CANCEL), note_stream int32 (0: notify upstream, else SUBS_NO_NOTE) --
+        the last four are encode_zmtp_multi's in_off, length, flags and
+        frame_stream with inp = plain and one stream.  results_out: a device
+        int64 tensor of n_streams x 4, read with subs_results().  clear_cnt
+        int32 [n_clear], clear_len int32 and clear_note uint8 [n_dst * cap].
+        flags: SUBS_VERBOSE, SUBS_VERBOSER."""
+        a, keep = self._subs_args(store, stream_dst, max_frames, results, frame_len, plain_off, flags_out, status_out,
+                                  plain, sub_status, topic_off, topic_len, note_flags, note_stream, results_out,
+                                  clear_dst, clear_cnt, clear_len, clear_note, flags)
+        self._check(_lib.zmqg_subs_update_multi(self._ctx, ctypes.byref(a), _stream_handle(stream)),
+                    "zmqg_subs_update_multi")
+        del keep
+
+    @staticmethod
+    def subs_results(results_out):
+        """subs_update_multi's `results_out` (synchronised) as a list of dicts, one per stream."""
+        r = results_out.cpu().numpy().view(np.uint64).reshape(-1, 4)
+        return [dict(seen=int(x[0]), changed=int(x[1]), notes=int(x[2]), rejected=int(x[3])) for x in r]
 
     @staticmethod
     def forward_router_pair_base(flags, route_idx, carry_idx, max_frames):
