@@ -56,6 +56,9 @@
  *   router_t::xrecv / xsend, lookup_out_pipe
  *     src/router.cpp:263-332, :161-261,
  *     src/socket_base.cpp:2187-2200                  zmqg_forward_zmtp_router_multi
+ *   lb_t::sendpipe (dealer_t::sendpipe, push_t::xsend)
+ *     src/lb.cpp:56-131, src/dealer.cpp:110-113,
+ *     src/push.cpp:45-48                             zmqg_forward_zmtp_lb_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -712,7 +715,9 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
  * before the encode's own), whatever the sizes are.  WebSocket framing on
  * either side is not offered on this call; routing by XPUB topics is
  * zmqg_forward_zmtp_sub_multi, routing by ROUTER identities
- * zmqg_forward_zmtp_router_multi. */
+ * zmqg_forward_zmtp_router_multi, DEALER's and PUSH's round-robin choice per
+ * message (lb_t) zmqg_forward_zmtp_lb_multi: route_dst is per stream and per
+ * call, and cannot give it. */
 typedef struct zmqg_forward_result {   /* per source stream, 32 bytes */
     uint64_t seq;         /* elements of the stream's sequence Q(s) */
     uint64_t held_first;  /* index in Q(s) of the first element not forwarded (== seq: none held) */
@@ -824,7 +829,8 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
  * the waves of heads walking their routes with a subscription a lane).  With
  * N == 0 the two are not queued.
  * Not offered: ROUTER identities (zmqg_forward_zmtp_router_multi, which does not
- * combine with this table); maintaining the table on the device from
+ * combine with this table); load balancing (zmqg_forward_zmtp_lb_multi, which
+ * does not either); maintaining the table on the device from
  * SUBSCRIBE / CANCEL commands (they stay held commands for the host;
  * zmqg_subs_update_multi, a call of its own, keeps such a table);
  * ZMQ_XPUB_MANUAL, ZMQ_XPUB_NODROP and high-water marks, the welcome message;
@@ -1109,8 +1115,9 @@ int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *st
  * queued.
  * Not offered: ZMQ_ROUTER_MANDATORY and its errors, ZMQ_ROUTER_HANDOVER,
  * ZMQ_ROUTER_RAW; maintaining the id table on the device; DEALER's round-robin
- * choice (lb_t), which the host makes through route_dst; high-water marks;
- * WebSocket framing; combining with the subscription table. */
+ * choice (lb_t), which is zmqg_forward_zmtp_lb_multi (with its own PREPEND for
+ * a ROUTER frontend); high-water marks; WebSocket framing; combining with the
+ * subscription table. */
 #define ZMQG_ROUTER_PREPEND 1u   /* receive side is a ROUTER: router_t::xrecv */
 #define ZMQG_ROUTER_ROUTE   2u   /* send side is a ROUTER: router_t::xsend */
 #define ZMQG_ROUTE_NONE      0xffffffffu  /* slot not forwarded (held, command, past seq, unused id slot) */
@@ -1131,6 +1138,120 @@ typedef struct zmqg_forward_router {
 } zmqg_forward_router;
 int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
                                    const zmqg_forward_router *router, void *stream);
+
+/* zmqg_forward_zmtp_lb_multi: zmqg_forward_zmtp_multi for a proxy whose send
+ * side is a DEALER or a PUSH socket -- the backend of a request/reply broker, a
+ * streamer.  Such a socket sends through lb_t (dealer_t::sendpipe,
+ * src/dealer.cpp:110-113, push_t::xsend, src/push.cpp:45-48): every whole
+ * message goes to the next active pipe in turn (lb_t::sendpipe,
+ * src/lb.cpp:56-131).  The turn is taken per message, which route_dst -- per
+ * source stream and per call -- cannot express: the host does not know how many
+ * messages a receive buffer holds until the decode has run.  Here the choice is
+ * made on the device between the decode and the encode, and the cursor stays
+ * there between calls.  With ZMQG_LB_PREPEND the receive side is a ROUTER, as
+ * under ZMQG_ROUTER_PREPEND: a ROUTER/DEALER broker is this call one way and
+ * zmqg_forward_zmtp_router_multi with ROUTE the other.  `args` is
+ * zmqg_forward_zmtp_multi's struct.
+ *
+ * Base behaviour.  Everything zmqg_forward_zmtp_multi states holds -- the
+ * receive side, Q(s), F, E, fwd[s] (unchanged: `forwarded` counts what the rule
+ * lets through), the carry, the send side as zmqg_encode_zmtp_multi over the
+ * pairs, fit and ENOBUFS, nonces in pair order -- with two changes: the pair
+ * space, and which pairs are live.  Data elements, heads and messages are
+ * defined as in zmqg_forward_zmtp_sub_multi; every message below held_first is
+ * complete, and there is one message per forwarded head.
+ *
+ * Pair space.  route_idx and route_dst are not read and may be NULL; every
+ * stream has one route slot, as under ZMQG_ROUTER_ROUTE.  m = 2 with PREPEND,
+ * else 1.  Stream s owns m * (c(s) + max_frames) pairs, base(s) is the running
+ * sum, p = base(s) + slot.  With m = 1 slot q is element q; with m = 2 slot
+ * 2q + 1 is element q and slot 2q the id part in front of it, {flags MORE,
+ * payload plain[src_id_off[s] .. +src_id_len[s])} (zmqg_forward_zmtp_router_
+ * multi's layout with d' = 1, and its rules for the ids).  N = base(n_streams)
+ * <= 2^31 - 1; pair_off has N + 1 entries, pair_status and dest_out N.
+ *
+ * The table.  A group is one load balancer: one DEALER or PUSH socket the
+ * thread serves.  stream_group[s] (a HOST array) names the group that
+ * distributes stream s's messages, or ZMQG_LB_NO_GROUP.  Group g's active
+ * destinations are lb_dst[grp_idx[g] .. grp_idx[g + 1]), indices into dst_sid:
+ * lb_t's _pipes[0 .. _active), in its order.  lb_cur[g] is lb_t's _current.
+ * grp_idx, lb_dst and lb_cur live on the device across calls; they are not HOST
+ * arrays and the call copies nothing of them.  The host rewrites the table in
+ * stream order when a worker connects, leaves or stops being writable.  The
+ * device trusts none of it: grp_idx entries above n_lb are clamped to n_lb, a
+ * falling pair of grp_idx entries is an empty range; A(g) is the size of group
+ * g's range, cur0(g) = lb_cur[g] mod A(g), or 0 when A(g) = 0; no element
+ * outside grp_idx[0 .. n_groups], lb_dst[0 .. n_lb) and lb_cur[0 .. n_groups)
+ * is read or written.
+ *
+ * Choice.  The messages of group g are the forwarded messages of the streams
+ * with stream_group[s] == g, by rising stream and, within a stream, by rising
+ * element: the order in which zmqg_forward_zmtp_multi lays messages into a
+ * destination's run.  The i-th message of the group (from 0) goes to entry
+ * lb_dst[grp_idx[g] + (cur0 + i) mod A] (grp_idx[g] clamped), all its parts and
+ * with PREPEND its id part.  After the call lb_cur[g] = (cur0 + M(g)) mod A, M(g)
+ * the group's messages in this call, or 0 when A = 0.  lb_cur is written for
+ * every group, clamped, whether or not the group had streams.  That is
+ * lb_t::sendpipe with every write succeeding: _pipes[_current] takes the
+ * message, and ++_current wraps at _active after its last part
+ * (src/lb.cpp:118-124); _more and _dropping never carry over between calls,
+ * because only whole messages are forwarded.  Order: the reference's fq_t hands
+ * lb_t the sources' messages interleaved by arrival (fq_t::recvpipe,
+ * src/fq.cpp:52-94); stream-major order is one such arrival order, fixed here
+ * so that the call is deterministic.
+ *
+ * Live pairs.  An element slot is live when its element is forwarded, its
+ * stream has a group, A(g) > 0 and the chosen entry's value t is below n_dst;
+ * its destination is t.  An id slot is live when its element is a forwarded
+ * head, under the same conditions.  A message whose entry names no destination
+ * (t >= n_dst) still takes its turn: the cursor moves past it.  A pair that is
+ * not live is zmqg_forward_zmtp_multi's: no stream, pair_status
+ * ZMQG_ERR_SESSION, pair_off UINT64_MAX, no nonce, no byte of `out`.
+ * dest_out[p] (device-accessible, N entries, or NULL): t for a live pair (also
+ * when t's session is invalid and the encode reports ZMQG_ERR_SESSION);
+ * ZMQG_LB_NO_PEER for every slot of a forwarded element, or of the id in front
+ * of a forwarded head, that is not live -- the host re-offers those messages as
+ * carries in a later call: they are whole and still in `plain`; ZMQG_LB_NONE
+ * for everything else.
+ *
+ * Returns -EINVAL for a null lb, size != sizeof(zmqg_forward_lb), flag bits
+ * other than ZMQG_LB_PREPEND; with PREPEND and n_streams > 0 a null src_id_off
+ * or src_id_len; n_groups or n_lb above 2^31 - 1; with n_groups > 0 a null
+ * grp_idx or lb_cur; a null lb_dst with n_lb > 0; with n_streams > 0 a null
+ * stream_group or an entry that is neither below n_groups nor
+ * ZMQG_LB_NO_GROUP; N > 0 with n_dst == 0; and every case of
+ * zmqg_forward_zmtp_multi, the route_idx / route_dst cases skipped and N
+ * computed as above; nothing is queued then.  With n_streams == 0 nothing is
+ * done and lb_cur is left alone.
+ * Launches: zmqg_forward_zmtp_multi's and two more, whatever the sizes are
+ * (one wave per source stream for the heads and, in the same pass, the
+ * messages' ranks; one wave per group for the streams' ring positions and the
+ * cursors); the pairs launch is this call's own.  With N == 0 the heads and the
+ * pairs are not queued, and the groups' launch, which then only clamps lb_cur,
+ * is queued when n_groups > 0.
+ * Not offered: high-water marks and lb_t's deactivation of a full pipe
+ * (src/lb.cpp:103-107): the host keeps a pipe that is not writable out of
+ * lb_dst; the exact turn after a membership change (the host edits the range
+ * without reading the cursor, the device clamps it); WebSocket framing;
+ * combining with the subscription or the id table. */
+#define ZMQG_LB_PREPEND  1u           /* receive side is a ROUTER: as ZMQG_ROUTER_PREPEND */
+#define ZMQG_LB_NO_GROUP 0xffffffffu  /* stream_group[s]: this stream's messages are not distributed */
+#define ZMQG_LB_NONE     0xffffffffu  /* dest_out: slot not forwarded (held, command, past seq, unused id slot) */
+#define ZMQG_LB_NO_PEER  0xfffffffdu  /* dest_out: part of a forwarded message that found no destination */
+typedef struct zmqg_forward_lb {      /* 80 bytes */
+    uint32_t size, flags;             /* sizeof(zmqg_forward_lb); 0 or ZMQG_LB_PREPEND */
+    const uint64_t *src_id_off;       /* PREPEND: n_streams, as zmqg_forward_router's */
+    const uint32_t *src_id_len;
+    uint64_t n_groups;                /* load balancers (one per DEALER / PUSH socket the thread serves) */
+    const uint32_t *stream_group;     /* HOST, n_streams: < n_groups, or ZMQG_LB_NO_GROUP */
+    const uint32_t *grp_idx;          /* device, n_groups + 1: group g's active destinations are lb_dst[grp_idx[g] .. grp_idx[g+1]) */
+    uint64_t n_lb;                    /* entries of lb_dst (<= 2^31 - 1) */
+    const uint32_t *lb_dst;           /* device: indices into dst_sid, lb_t's _pipes[0 .. _active) per group */
+    uint32_t *lb_cur;                 /* device, n_groups: lb_t's _current, read and written by the call */
+    uint32_t *dest_out;               /* device, N entries, or NULL */
+} zmqg_forward_lb;
+int zmqg_forward_zmtp_lb_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
+                               const zmqg_forward_lb *lb, void *stream);
 
 /* WebSocket framing (ZWS 2.0 over RFC 6455): the reference's second caller of
  * the mechanism, ws_engine_t::decode_and_push (src/ws_engine.cpp:887-915),

@@ -94,13 +94,19 @@ struct ZmtpWs {
     DevBuf<uint64_t> p_off;     // [p_cap] its payload's offset in `plain`
     DevBuf<uint32_t> p_len;     // [p_cap] and length
     DevBuf<uint32_t> p_tab;     // the call's host arrays: bases, carry_idx, route_idx [3][streams + 1], route_dst
-                                // (zmqg_forward_zmtp_sub_multi / _router_multi: [4], the element bases behind route_idx)
+                                // (zmqg_forward_zmtp_sub_multi / _router_multi / _lb_multi: [4], the element bases
+                                // behind route_idx; _lb_multi: then stream_group and the group-to-streams lists)
     uint64_t m_cap = 0;         // zmqg_forward_zmtp_sub_multi: pairs
     DevBuf<uint8_t> p_match;    // [m_cap] at a head's pairs: its route's destination is subscribed to the topic
     uint64_t e_cap = 0;         // and elements of the routed streams
     DevBuf<uint32_t> e_head;    // [e_cap] the index in Q(s) of each forwarded element's head
     uint64_t v_cap = 0;         // zmqg_forward_zmtp_router_multi with ROUTE: elements
     DevBuf<uint32_t> e_verdict; // [v_cap] at a head: the destination its address names, or UNKNOWN / MALFORMED
+    uint64_t l_cap = 0;         // zmqg_forward_zmtp_lb_multi: elements
+    DevBuf<uint32_t> e_rank;    // [l_cap] at a forwarded data element: the rank of its message within the stream
+    uint64_t ls_cap = 0;        // and source streams
+    DevBuf<uint32_t> s_msgs;    // [ls_cap] the stream's forwarded messages
+    DevBuf<uint32_t> s_first;   // [ls_cap] the ring position of its first message
     uint64_t u_cap = 0;         // zmqg_subs_update_multi: events (cleared slots, then the decode call's slots)
     DevBuf<uint32_t> u_h0;      // [u_cap] the slots holding the event's topic at call start
     DevBuf<int8_t> u_delta;     // [u_cap] what the event did to its destination's hold on the topic: +1 / -1 / 0

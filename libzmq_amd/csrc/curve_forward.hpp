@@ -32,6 +32,10 @@
 // kernels between the scan and the pairs (curve_fwd_match.hpp).
 // zmqg_forward_zmtp_router_multi has the same fourth row, the heads, a lookup
 // of every head's address and a pairs kernel of its own (curve_fwd_route.hpp).
+// zmqg_forward_zmtp_lb_multi has the fourth row too, behind the table
+// stream_group and the group-to-streams lists, the heads with the messages'
+// ranks, the groups' ring positions and a pairs kernel of its own
+// (curve_fwd_lb.hpp).
 #pragma once
 
 #include <stdint.h>

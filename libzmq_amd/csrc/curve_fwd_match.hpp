@@ -12,7 +12,9 @@
 //                element below held_first the index in Q(s) of its message's
 //                head (the first data element, and every data element whose
 //                predecessor among the data elements has MORE clear), a
-//                running maximum over "is a head" from ballots
+//                running maximum over "is a head" from ballots (and for the
+//                load balancer, curve_fwd_lb.hpp, each message's rank within
+//                the stream from prefix popcounts of the same ballot)
 //   k_fwd_match  one wave per element; the waves of heads stay: the topic's
 //                first kFwdTopicWin bytes staged in LDS; then, 64 routes a
 //                round, every lane fetches its route's range of subscriptions,
@@ -100,24 +102,33 @@ __device__ __forceinline__ int fwd_top_at(uint64_t m, uint32_t l)
 
 // ebase[s] = the first element of stream s in `head` (streams without routes
 // have none); runs behind k_fwd_scan, whose held_first bounds what is written.
+// kRank (zmqg_forward_zmtp_lb_multi, curve_fwd_lb.hpp): the same ballots also
+// give rank[ebase[s] + q], for forwarded data elements, the number of heads of
+// the stream before its message's head, and msgs[s], the stream's heads.
+template <bool kRank>
 __global__ __launch_bounds__(kFwdThreads) void k_fwd_heads(uint32_t n_streams, uint64_t max_frames,
                                                           const uint32_t *__restrict__ cidx,
                                                           const uint32_t *__restrict__ ebase,
                                                           const uint8_t *__restrict__ carry_flags,
                                                           const uint8_t *__restrict__ flags_out,
                                                           const zmqg_forward_result *__restrict__ fwd,
-                                                          uint32_t *__restrict__ head)
+                                                          uint32_t *__restrict__ head, uint32_t *__restrict__ rank,
+                                                          uint32_t *__restrict__ msgs)
 {
     const uint32_t lane = threadIdx.x & 63u, s = blockIdx.x * (kFwdThreads / 64u) + (threadIdx.x >> 6);
     if (s >= n_streams)
         return; // (the whole wave)
     const uint32_t e0 = ebase[s];
-    if (ebase[s + 1] == e0)
-        return; // no routes: no pairs read it
+    if (ebase[s + 1] == e0) { // no routes: no pairs read it
+        if (kRank && lane == 0)
+            msgs[s] = 0;
+        return;
+    }
     const uint32_t c0 = cidx[s], c = cidx[s + 1] - c0;
     const uint64_t lim = fwd[s].held_first, slot0 = (uint64_t) s * max_frames; // (below F: every frame has status 0)
     bool closed = true;          // the last data element before this step has MORE clear (or there is none)
     uint32_t last = kFwdNoHead;  // the last head before this step
+    uint32_t before = 0;         // kRank: the heads before this step
     for (uint64_t q0 = 0; q0 < lim; q0 += 64u) {
         const uint64_t q = q0 + lane;
         const bool in = q < lim;
@@ -132,11 +143,18 @@ __global__ __launch_bounds__(kFwdThreads) void k_fwd_heads(uint32_t n_streams, u
         const int h = fwd_top_at(headm, lane);
         if (in)
             head[e0 + q] = h < 0 ? last : (uint32_t) (q0 + (uint32_t) h);
+        if (kRank) { // (a data element has its head at or before it: the count is at least 1)
+            if (part)
+                rank[e0 + q] = before + (uint32_t) __builtin_popcountll(headm & ((2ull << lane) - 1ull)) - 1u;
+            before += (uint32_t) __builtin_popcountll(headm);
+        }
         if (partm)
             closed = (lastm >> (63 - __builtin_clzll(partm))) & 1ull;
         if (headm)
             last = (uint32_t) (q0 + (uint32_t) (63 - __builtin_clzll(headm)));
     }
+    if (kRank && lane == 0)
+        msgs[s] = before;
 }
 
 // One wave per element e of the element space; s by a search of ebase as

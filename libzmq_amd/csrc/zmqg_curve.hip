@@ -61,6 +61,7 @@
 #include "curve_forward.hpp"
 #include "curve_fwd_match.hpp"
 #include "curve_fwd_route.hpp"
+#include "curve_fwd_lb.hpp"
 #include "curve_subs.hpp"
 #include "curve_ws.hpp"
 
@@ -3375,15 +3376,25 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
 // checked by the caller; never together with subs) the pairs are the router pair
 // space (curve_fwd_route.hpp): the heads, with ROUTE the lookup of every head's
 // address, and the router's own pairs kernel in place of k_fwd_pairs.
+// With `lb` (zmqg_forward_zmtp_lb_multi, its own fields checked by the caller;
+// never together with subs or rt) every stream has one route slot, the table
+// also carries stream_group and the group-to-streams lists, and the plan is the
+// heads with the messages' ranks, the groups and the load balancer's own pairs
+// kernel (curve_fwd_lb.hpp).
 static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
-                              const zmqg_forward_router *rt, void *stream)
+                              const zmqg_forward_router *rt, const zmqg_forward_lb *lb, void *stream)
 {
+    static_assert(kFwdLbNone == ZMQG_LB_NONE && kFwdLbNoPeer == ZMQG_LB_NO_PEER &&
+                      kFwdLbNoGroup == ZMQG_LB_NO_GROUP && kFwdLbPrepend == ZMQG_LB_PREPEND,
+                  "curve_fwd_lb.hpp restates the header's values");
     static_assert(kFwdRouteNone == ZMQG_ROUTE_NONE && kFwdRouteAddress == ZMQG_ROUTE_ADDRESS &&
                       kFwdRouteUnknown == ZMQG_ROUTE_UNKNOWN && kFwdRouteMalformed == ZMQG_ROUTE_MALFORMED &&
                       kFwdRouterPrepend == ZMQG_ROUTER_PREPEND && kFwdRouterRoute == ZMQG_ROUTER_ROUTE,
                   "curve_fwd_route.hpp restates the header's values");
-    const bool route = rt && (rt->flags & ZMQG_ROUTER_ROUTE), prepend = rt && (rt->flags & ZMQG_ROUTER_PREPEND);
-    const uint64_t slots_m = prepend && !route ? 2u : 1u; // m: an id slot in front of every element
+    // route: one route slot a stream, route_idx / route_dst not read (ROUTE, or the load balancer)
+    const bool route = (rt && (rt->flags & ZMQG_ROUTER_ROUTE)) || lb;
+    const bool prepend = (rt && (rt->flags & ZMQG_ROUTER_PREPEND)) || (lb && (lb->flags & ZMQG_LB_PREPEND));
+    const uint64_t slots_m = prepend && (lb || !route) ? 2u : 1u; // m: an id slot in front of every element
     if (!ctx || !args || args->size != sizeof *args || args->reserved != 0)
         return -EINVAL;
     const zmqg_forward_zmtp &a = *args;
@@ -3439,11 +3450,31 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
     // one copy to the device, where every pair searches them
     // (with subs a fourth row: ebase, each routed stream's first element among
     // the elements of the routed streams -- at most N of them)
-    const size_t rows = subs || rt ? 4 : 3, words = rows * (size_t) (S + 1) + R;
+    // (with lb behind them: stream_group [S], then the streams of every group,
+    // rising within a group, as an index [n_groups + 1] and a list [SG])
+    const uint64_t G = lb ? lb->n_groups : 0u;
+    uint64_t SG = 0; // the streams that have a group
+    for (uint64_t s = 0; lb && s < S; ++s)
+        SG += lb->stream_group[s] != ZMQG_LB_NO_GROUP;
+    const size_t rows = subs || rt || lb ? 4 : 3,
+                 words = rows * (size_t) (S + 1) + R + (lb ? (size_t) S + (size_t) (G + 1) + (size_t) SG : 0u);
     if ((rc = sinst_room(ctx, 4 * words)))
         return rc;
     uint32_t *h_base = (uint32_t *) ctx->sinst, *h_cidx = h_base + (S + 1), *h_ridx = h_cidx + (S + 1),
              *h_ebase = h_ridx + (S + 1), *h_rdst = h_base + rows * (S + 1);
+    if (lb) {
+        uint32_t *h_sgrp = h_rdst, *h_gidx = h_sgrp + S, *h_gstr = h_gidx + (G + 1);
+        memcpy(h_sgrp, lb->stream_group, 4 * (size_t) S);
+        memset(h_gidx, 0, 4 * (size_t) (G + 1));
+        for (uint64_t s = 0; s < S; ++s) // counts, one slot up
+            if (h_sgrp[s] != ZMQG_LB_NO_GROUP && h_sgrp[s] + 1u < G)
+                ++h_gidx[h_sgrp[s] + 2u];
+        for (uint64_t g = 2; g <= G; ++g) // h_gidx[g + 1] = the first stream of group g
+            h_gidx[g] += h_gidx[g - 1];
+        for (uint64_t s = 0; s < S; ++s) // h_gidx[g + 1] walks up to the end of group g
+            if (h_sgrp[s] != ZMQG_LB_NO_GROUP)
+                h_gstr[h_gidx[h_sgrp[s] + 1u]++] = (uint32_t) s;
+    }
     uint32_t b = 0, eb = 0;
     for (uint64_t s = 0; s <= S; ++s) {
         h_base[s] = b;
@@ -3480,13 +3511,26 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
         ZRESERVE(ctx, z.p_match, cap, st);
         z.m_cap = cap;
     }
-    if ((subs || rt) && EN > z.e_cap) {
+    if (lb && EN > z.l_cap) {
+        const uint64_t cap = grown_cap(z.l_cap, 1024, EN);
+        z.l_cap = 0;
+        ZRESERVE(ctx, z.e_rank, cap, st);
+        z.l_cap = cap;
+    }
+    if (lb && S > z.ls_cap) {
+        const uint64_t cap = grown_cap(z.ls_cap, 1024, S);
+        z.ls_cap = 0;
+        ZRESERVE(ctx, z.s_msgs, cap, st);
+        ZRESERVE(ctx, z.s_first, cap, st);
+        z.ls_cap = cap;
+    }
+    if ((subs || rt || lb) && EN > z.e_cap) {
         const uint64_t cap = grown_cap(z.e_cap, 1024, EN);
         z.e_cap = 0;
         ZRESERVE(ctx, z.e_head, cap, st);
         z.e_cap = cap;
     }
-    if (route && EN > z.v_cap) {
+    if (route && !lb && EN > z.v_cap) {
         const uint64_t cap = grown_cap(z.v_cap, 1024, EN);
         z.v_cap = 0;
         ZRESERVE(ctx, z.e_verdict, cap, st);
@@ -3510,9 +3554,10 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
     if (N > 0 && subs) {
         // the heads (one wave per source stream), then each head's topic against
         // its routes' subscriptions (one wave per element; N > 0: EN > 0)
-        hipLaunchKernelGGL(k_fwd_heads, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
+        hipLaunchKernelGGL(k_fwd_heads<false>, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
                            dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
-                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p);
+                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p,
+                           (uint32_t *) nullptr, (uint32_t *) nullptr);
         ZCHECK(ctx, hipGetLastError());
         const uint64_t per = kFwdMatchThreads / 64u;
         hipLaunchKernelGGL(k_fwd_match, dim3((unsigned) ((EN + per - 1) / per)), dim3(kFwdMatchThreads), 0, st,
@@ -3530,12 +3575,44 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
                            z.p_flags.p, z.p_off.p, z.p_len.p, d_ebase, (const uint32_t *) z.e_head.p,
                            (const uint8_t *) z.p_match.p, subs->match_out);
         ZCHECK(ctx, hipGetLastError());
+    } else if (lb) {
+        // the heads with the rank of every message within its stream, every
+        // stream's ring position and every group's new cursor, the pairs (one
+        // wave per source stream; one wave per group; one lane per pair).
+        // Without pairs the groups alone, which then only clamp the cursors.
+        const uint32_t *d_sgrp = d_rdst, *d_gidx = d_sgrp + S, *d_gstr = d_gidx + (G + 1);
+        if (N > 0) {
+            hipLaunchKernelGGL(k_fwd_heads<true>, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
+                               dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
+                               (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p,
+                               z.e_rank.p, z.s_msgs.p);
+            ZCHECK(ctx, hipGetLastError());
+        }
+        if (G > 0) {
+            hipLaunchKernelGGL(k_fwd_lb_groups, dim3((unsigned) ((G + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
+                               dim3(kFwdThreads), 0, st, (uint32_t) G, d_gidx, d_gstr,
+                               N > 0 ? (const uint32_t *) z.s_msgs.p : (const uint32_t *) nullptr, lb->grp_idx,
+                               (uint32_t) lb->n_lb, lb->lb_cur, z.s_first.p);
+            ZCHECK(ctx, hipGetLastError());
+        }
+        if (N > 0) {
+            hipLaunchKernelGGL(k_fwd_pairs_lb, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
+                               (uint32_t) S, MF, lb->flags & ZMQG_LB_PREPEND, d_base, d_cidx, d_ebase, d_sgrp,
+                               a.carry_off, a.carry_len, a.carry_flags, (const uint64_t *) a.plain_off,
+                               (const uint32_t *) a.frame_len, (const uint8_t *) a.flags_out,
+                               (const zmqg_forward_result *) a.fwd, (const uint32_t *) z.e_head.p,
+                               (const uint32_t *) z.e_rank.p, (const uint32_t *) z.s_first.p, lb->grp_idx,
+                               (uint32_t) lb->n_lb, lb->lb_dst, a.n_dst, lb->src_id_off, lb->src_id_len, z.p_stream.p,
+                               z.p_flags.p, z.p_off.p, z.p_len.p, lb->dest_out);
+            ZCHECK(ctx, hipGetLastError());
+        }
     } else if (N > 0 && rt) {
         // the heads; with ROUTE the lookup of every head's address (one wave per
         // element; N > 0: EN > 0); the router pair space
-        hipLaunchKernelGGL(k_fwd_heads, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
+        hipLaunchKernelGGL(k_fwd_heads<false>, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
                            dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
-                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p);
+                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p,
+                           (uint32_t *) nullptr, (uint32_t *) nullptr);
         ZCHECK(ctx, hipGetLastError());
         if (route) {
             const uint64_t per = kFwdRouteThreads / 64u;
@@ -3577,7 +3654,7 @@ static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
 
 int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
 {
-    return forward_multi_impl(ctx, args, nullptr, nullptr, stream);
+    return forward_multi_impl(ctx, args, nullptr, nullptr, nullptr, stream);
 }
 
 // The table's launch-free checks; what the host cannot see (sub_idx's entries,
@@ -3590,7 +3667,7 @@ int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, co
     if (check_n(subs->n_subs) || (args->n_dst > 0 && !subs->sub_idx) ||
         (subs->n_subs > 0 && (!subs->sub_off || !subs->sub_len)) || (subs->sub_bytes_len > 0 && !subs->sub_bytes))
         return -EINVAL;
-    return forward_multi_impl(ctx, args, subs, nullptr, stream);
+    return forward_multi_impl(ctx, args, subs, nullptr, nullptr, stream);
 }
 
 // The router struct's launch-free checks; the id table's contents the lookup
@@ -3607,7 +3684,29 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
         (check_n(router->n_ids) || (router->n_ids > 0 && (!router->id_off || !router->id_len || !router->id_dst)) ||
          (router->id_bytes_len > 0 && !router->id_bytes)))
         return -EINVAL;
-    return forward_multi_impl(ctx, args, nullptr, router->flags ? router : nullptr, stream);
+    return forward_multi_impl(ctx, args, nullptr, router->flags ? router : nullptr, nullptr, stream);
+}
+
+// The load balancer's launch-free checks: the struct, and stream_group, the one
+// array of it the host can see.  grp_idx, lb_dst and lb_cur live on the device;
+// the kernels bound every read of them (curve_fwd_lb.hpp).
+int zmqg_forward_zmtp_lb_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_lb *lb, void *stream)
+{
+    if (!ctx || !args || !lb || lb->size != sizeof *lb || (lb->flags & ~ZMQG_LB_PREPEND) != 0)
+        return -EINVAL;
+    if ((lb->flags & ZMQG_LB_PREPEND) && args->n_streams > 0 && (!lb->src_id_off || !lb->src_id_len))
+        return -EINVAL;
+    if (check_n(lb->n_groups) || check_n(lb->n_lb) || (lb->n_groups > 0 && (!lb->grp_idx || !lb->lb_cur)) ||
+        (lb->n_lb > 0 && !lb->lb_dst))
+        return -EINVAL;
+    if (args->size != sizeof *args || check_n(args->n_streams)) // (before stream_group is walked)
+        return -EINVAL;
+    if (args->n_streams > 0 && !lb->stream_group)
+        return -EINVAL;
+    for (uint64_t s = 0; s < args->n_streams; ++s)
+        if (lb->stream_group[s] != ZMQG_LB_NO_GROUP && lb->stream_group[s] >= lb->n_groups)
+            return -EINVAL;
+    return forward_multi_impl(ctx, args, nullptr, nullptr, lb, stream);
 }
 
 // The launch-free checks, the two host arrays through the pinned staging, then

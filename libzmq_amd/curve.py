@@ -162,6 +162,17 @@ class ForwardRouter(ctypes.Structure):  # zmqg_forward_router
                 ("dest_out", _P)]
 
 
+LB_PREPEND = 1  # ZMQG_LB_PREPEND
+LB_NO_GROUP, LB_NONE, LB_NO_PEER = 0xffffffff, 0xffffffff, 0xfffffffd  # ZMQG_LB_*
+
+
+class ForwardLb(ctypes.Structure):  # zmqg_forward_lb
+    _fields_ = [("size", _U32), ("flags", _U32), ("src_id_off", _P), ("src_id_len", _P), ("n_groups", _U64),
+                ("stream_group", _P), ("grp_idx", _P), ("n_lb", _U64), ("lb_dst", _P), ("lb_cur", _P),
+                ("dest_out", _P)]
+
+
+_lib.zmqg_forward_zmtp_lb_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardLb), _P]
 _lib.zmqg_forward_zmtp_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), _P]
 _lib.zmqg_forward_zmtp_router_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardRouter), _P]
 _lib.zmqg_forward_zmtp_sub_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardSubs), _P]
@@ -710,6 +721,54 @@ class CurveContext:
         self._check(_lib.zmqg_forward_zmtp_router_multi(self._ctx, ctypes.byref(a), ctypes.byref(rt),
                                                         _stream_handle(stream)), "zmqg_forward_zmtp_router_multi")
         del keep
+
+    @staticmethod
+    def forward_lb_pair_base(flags, carry_idx, max_frames, n_streams):
+        """base(s) of forward_zmtp_lb_multi's pairs, n_streams + 1 entries, the
+        last one N: stream s owns m * (c(s) + max_frames) pairs, m = 2 with
+        LB_PREPEND (an id slot in front of every element), else 1."""
+        m = 2 if flags & LB_PREPEND else 1
+        n = int(n_streams)
+        c = np.zeros(n, np.int64) if carry_idx is None else np.diff(np.asarray(carry_idx, np.int64))
+        return [0] + [int(x) for x in np.cumsum(m * (c + int(max_frames)))]
+
+    def forward_zmtp_lb_multi(self, stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                              frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, out, pair_off,
+                              pair_status, dst_results, fwd, flags, stream_group, grp_idx, lb_dst, lb_cur,
+                              n_groups=None, n_lb=None, src_id_off=None, src_id_len=None, dest_out=None,
+                              carry_idx=None, carry_off=None, carry_len=None, carry_flags=None, stream=None,
+                              out_bytes=None):
+        """forward_zmtp_multi for a proxy whose send side is a DEALER or a PUSH
+        socket (zmqg_forward_zmtp_lb_multi): every whole message goes to the
+        next active destination of its stream's group in turn, as lb_t does.
+        There are no routes.  stream_group: a host sequence of n_streams group
+        indices or LB_NO_GROUP, copied before the call returns.  grp_idx (int32,
+        n_groups + 1), lb_dst (int32, n_lb) and lb_cur (int32, n_groups) are
+        device tensors that live across calls: group g's active destinations
+        are lb_dst[grp_idx[g] .. grp_idx[g + 1]), lb_cur[g] its cursor, read
+        and written by the call (n_groups defaults to lb_cur's length, n_lb to
+        lb_dst's).  flags: 0 or LB_PREPEND (every message gets its source's
+        routing id in front: src_id_off int64 and src_id_len int32 device
+        tensors of n_streams, offsets into plain).  dest_out: a device int32
+        tensor of N entries (forward_lb_pair_base(...)[-1]) that receives each
+        pair's destination, LB_NO_PEER or LB_NONE, or None."""
+        a, keep = self._forward_args(stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                                     frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, None,
+                                     None, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
+                                     carry_len, carry_flags, out_bytes)
+        sg = None if stream_group is None else np.ascontiguousarray(stream_group, dtype=np.uint32)
+        if sg is not None and len(sg) != int(a.n_streams):
+            raise ValueError("stream_group holds n_streams entries")
+        if n_groups is None:
+            n_groups = 0 if lb_cur is None else int(lb_cur.numel())
+        if n_lb is None:
+            n_lb = 0 if lb_dst is None else int(lb_dst.numel())
+        lb = ForwardLb(ctypes.sizeof(ForwardLb), int(flags), _ptr(src_id_off), _ptr(src_id_len), int(n_groups),
+                       sg.ctypes.data if sg is not None and len(sg) else None, _ptr(grp_idx), int(n_lb),
+                       _ptr(lb_dst), _ptr(lb_cur), _ptr(dest_out))
+        self._check(_lib.zmqg_forward_zmtp_lb_multi(self._ctx, ctypes.byref(a), ctypes.byref(lb),
+                                                    _stream_handle(stream)), "zmqg_forward_zmtp_lb_multi")
+        del keep, sg
 
     @staticmethod
     def forward_results(fwd):
