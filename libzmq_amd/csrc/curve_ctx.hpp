@@ -93,9 +93,7 @@ struct ZmtpWs {
     DevBuf<uint8_t> p_flags;    // [p_cap] its MORE bit
     DevBuf<uint64_t> p_off;     // [p_cap] its payload's offset in `plain`
     DevBuf<uint32_t> p_len;     // [p_cap] and length
-    DevBuf<uint32_t> p_tab;     // the call's host arrays: bases, carry_idx, route_idx [3][streams + 1], route_dst
-                                // (zmqg_forward_zmtp_sub_multi / _router_multi / _lb_multi: [4], the element bases
-                                // behind route_idx; _lb_multi: then stream_group and the group-to-streams lists)
+    DevBuf<uint32_t> p_tab;     // the call's host arrays as one table (curve_fwd_common.hpp)
     uint64_t m_cap = 0;         // zmqg_forward_zmtp_sub_multi: pairs
     DevBuf<uint8_t> p_match;    // [m_cap] at a head's pairs: its route's destination is subscribed to the topic
     uint64_t e_cap = 0;         // and elements of the routed streams
@@ -185,6 +183,46 @@ struct zmqg_ctx {
 // it: a failure part-way leaves 0, the next call reserves again (the members
 // that grew are no-ops then), and no call ever runs on a half-grown group.
 #define ZRESERVE(ctx, buf, count, st) ZCHECK(ctx, (buf).reserve((ctx)->mem, (count), (st)))
+
+// The same for a group whose members all have `cap` elements; `names` is the
+// group as last_error reports it.
+template <class... Bufs>
+static int reserve_group(zmqg_ctx *ctx, hipStream_t st, const char *names, uint64_t &cap, uint64_t floor,
+                         uint64_t need, Bufs &...bufs)
+{
+    if (need <= cap)
+        return 0;
+    const uint64_t grown = grown_cap(cap, floor, need);
+    cap = 0;
+    hipError_t e = hipSuccess;
+    (void) (((e = bufs.reserve(ctx->mem, grown, st)) == hipSuccess) && ...); // (in order, up to the first failure)
+    if (e != hipSuccess) {
+        snprintf(ctx->last_error, sizeof ctx->last_error, "reserve_group(%s): %s", names, hipGetErrorString(e));
+        return -EIO;
+    }
+    cap = grown;
+    return 0;
+}
+
+// a grid of one wave per item, `threads` a workgroup
+static inline unsigned wave_grid(uint64_t n, uint32_t threads)
+{
+    const uint64_t per = threads / 64u;
+    return (unsigned) ((n + per - 1) / per);
+}
+
+// The decode's options for a receive side with this maxmsgsize, in *o, or null:
+// a maxmsgsize within the frame kernel's range bounds every frame, so the
+// large-frame launches are skipped.
+static inline const zmqg_batch_opts *decode_len_bound(int64_t max_msg_size, zmqg_batch_opts *o)
+{
+    if (max_msg_size < 0 || (uint64_t) max_msg_size > kMaxFrameStream)
+        return nullptr;
+    *o = zmqg_batch_opts{};
+    o->size = sizeof *o;
+    o->max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
+    return o;
+}
 
 // The ctx's work is ordered by stream: a batch call runs on the caller's
 // stream (which then becomes the ctx's last stream); every call that uses

@@ -9,12 +9,8 @@
 // the forwarded messages of its streams, by rising stream, then rising element;
 // the i-th of them takes ring position (cur0 + i) mod A.
 //
-//   k_fwd_heads<true>  (curve_fwd_match.hpp) one wave per source stream, 64
-//                    elements a step: the head of every forwarded element, and
-//                    from the ballot of "is a head" and prefix popcounts the
-//                    rank of every forwarded data element's message within the
-//                    stream, carried across steps, and the stream's messages
-//                    (the ranks fused into the heads pass: one launch fewer)
+//   k_fwd_heads<true>  (curve_fwd_match.hpp) the heads, with every message's
+//                    rank within its stream and the stream's messages
 //   k_fwd_lb_groups  one wave per group, 64 of its streams a step: a wave
 //                    exclusive sum of the message counts -> each stream's ring
 //                    position first[s], and the group's new cursor
@@ -26,19 +22,11 @@
 // and fwd_lb_pick bound every read of it; they also compile for the host
 // (tests/host/test_fwd_lb.cpp).
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define ZMQG_FWDL_FN __host__ __device__ inline
-#else
-#define ZMQG_FWDL_FN inline
-#endif
+#include "curve_fwd_common.hpp"
 
 namespace zmqg {
 
-constexpr uint32_t kFwdLbNone = 0xffffffffu;    // ZMQG_LB_NONE
-constexpr uint32_t kFwdLbNoPeer = 0xfffffffdu;  // ZMQG_LB_NO_PEER
-constexpr uint32_t kFwdLbNoGroup = 0xffffffffu; // ZMQG_LB_NO_GROUP
+constexpr uint32_t kFwdLbNone = ZMQG_LB_NONE, kFwdLbNoPeer = ZMQG_LB_NO_PEER, kFwdLbNoGroup = ZMQG_LB_NO_GROUP;
 
 // Group g's active destinations lb_dst[lo .. lo + A): grp_idx entries above n_lb
 // clamped to it, a falling pair an empty range.
@@ -46,7 +34,7 @@ struct FwdLbRange {
     uint32_t lo, A;
 };
 
-ZMQG_FWDL_FN FwdLbRange fwd_lb_range(uint32_t idx_lo, uint32_t idx_hi, uint32_t n_lb)
+ZMQG_FWD_FN FwdLbRange fwd_lb_range(uint32_t idx_lo, uint32_t idx_hi, uint32_t n_lb)
 {
     const uint32_t lo = idx_lo < n_lb ? idx_lo : n_lb;
     const uint32_t hi = idx_hi < n_lb ? idx_hi : n_lb;
@@ -58,14 +46,14 @@ ZMQG_FWDL_FN FwdLbRange fwd_lb_range(uint32_t idx_lo, uint32_t idx_hi, uint32_t 
 
 // lb_t's _current of a cursor the host may have left anywhere (the range was
 // edited without reading it): cur mod A, 0 for an empty range.
-ZMQG_FWDL_FN uint32_t fwd_lb_cur0(uint32_t cur, uint32_t A)
+ZMQG_FWD_FN uint32_t fwd_lb_cur0(uint32_t cur, uint32_t A)
 {
     return A ? cur % A : 0u;
 }
 
 // The ring position `add` messages after pos (pos < A <= 2^31 - 1, add below
 // 2^62: a sum of per-stream counts), in 64-bit arithmetic; 0 for an empty range.
-ZMQG_FWDL_FN uint32_t fwd_lb_at(uint32_t pos, uint64_t add, uint32_t A)
+ZMQG_FWD_FN uint32_t fwd_lb_at(uint32_t pos, uint64_t add, uint32_t A)
 {
     return A ? (uint32_t) (((uint64_t) pos + add) % A) : 0u;
 }
@@ -73,7 +61,7 @@ ZMQG_FWDL_FN uint32_t fwd_lb_at(uint32_t pos, uint64_t add, uint32_t A)
 // The destination at ring position pos (< A) of the range, or kFwdLbNoPeer for
 // an entry that names none (>= n_dst).  The read is lb_dst[lo + pos] with lo +
 // pos < lo + A <= n_lb.
-ZMQG_FWDL_FN uint32_t fwd_lb_pick(const uint32_t *lb_dst, const FwdLbRange &r, uint32_t pos, uint64_t n_dst)
+ZMQG_FWD_FN uint32_t fwd_lb_pick(const uint32_t *lb_dst, const FwdLbRange &r, uint32_t pos, uint64_t n_dst)
 {
     const uint32_t t = lb_dst[(uint64_t) r.lo + pos];
     return t < n_dst ? t : kFwdLbNoPeer;
@@ -81,7 +69,7 @@ ZMQG_FWDL_FN uint32_t fwd_lb_pick(const uint32_t *lb_dst, const FwdLbRange &r, u
 
 #if defined(__HIPCC__)
 
-constexpr uint32_t kFwdLbPrepend = 1u; // ZMQG_LB_PREPEND
+constexpr uint32_t kFwdLbPrepend = ZMQG_LB_PREPEND;
 
 // One wave per group.  gstr[gidx[g] .. gidx[g + 1]) are the group's streams,
 // rising.  first[s] = (cur0 + the group's messages before stream s) mod A, and
@@ -107,12 +95,7 @@ __global__ __launch_bounds__(kFwdThreads) void k_fwd_lb_groups(uint32_t n_groups
         const bool in = i < end;
         const uint32_t s = in ? gstr[i] : 0u;
         const uint64_t cnt = in ? msgs[s] : 0u;
-        uint64_t incl = cnt; // the inclusive sum over the lanes (each at most 2^31 - 1)
-        for (uint32_t o = 1; o < 64u; o <<= 1) {
-            const uint64_t up = __shfl_up((unsigned long long) incl, o, 64);
-            if (lane >= o)
-                incl += up;
-        }
+        const uint64_t incl = wave_incl_sum_u64(cnt, lane); // (each at most 2^31 - 1)
         if (in)
             first[s] = fwd_lb_at(cur0, before + (incl - cnt), r.A);
         before += (uint64_t) __shfl((unsigned long long) incl, 63, 64);
@@ -121,54 +104,28 @@ __global__ __launch_bounds__(kFwdThreads) void k_fwd_lb_groups(uint32_t n_groups
         lb_cur[g] = fwd_lb_at(cur0, before, r.A);
 }
 
-// One lane per pair: stream s owns m * (c(s) + max_frames) pairs, m = 2 with
-// prepend (slot 2q + 1 is element q, slot 2q the id part in front of it), else
-// 1.  sgrp[s] is the stream's group (below n_groups, checked on the host) or
-// kFwdLbNoGroup.
+// One lane per pair: one route slot a stream, id slots with prepend.  sgrp[s] is
+// the stream's group (below n_groups, checked on the host) or kFwdLbNoGroup.
+// Destination rule: the ring position of the element's message in its stream's
+// group, an id part only in front of a head.
 __global__ __launch_bounds__(256) void k_fwd_pairs_lb(
-    uint32_t n, uint32_t n_streams, uint64_t max_frames, uint32_t prepend, const uint32_t *__restrict__ base,
-    const uint32_t *__restrict__ cidx, const uint32_t *__restrict__ ebase, const uint32_t *__restrict__ sgrp,
-    const uint64_t *__restrict__ carry_off, const uint32_t *__restrict__ carry_len,
-    const uint8_t *__restrict__ carry_flags, const uint64_t *__restrict__ plain_off,
-    const uint32_t *__restrict__ frame_len, const uint8_t *__restrict__ flags_out,
-    const zmqg_forward_result *__restrict__ fwd, const uint32_t *__restrict__ head, const uint32_t *__restrict__ rank,
-    const uint32_t *__restrict__ first, const uint32_t *__restrict__ grp_idx, uint32_t n_lb,
-    const uint32_t *__restrict__ lb_dst, uint64_t n_dst, const uint64_t *__restrict__ src_id_off,
-    const uint32_t *__restrict__ src_id_len, uint32_t *__restrict__ p_stream, uint8_t *__restrict__ p_flags,
-    uint64_t *__restrict__ p_off, uint32_t *__restrict__ p_len, uint32_t *__restrict__ dest_out)
+    uint32_t n, FwdSrc src, FwdTab tab, uint32_t prepend, const uint32_t *__restrict__ sgrp,
+    const uint32_t *__restrict__ head, const uint32_t *__restrict__ rank, const uint32_t *__restrict__ first,
+    const uint32_t *__restrict__ grp_idx, uint32_t n_lb, const uint32_t *__restrict__ lb_dst, uint64_t n_dst,
+    const uint64_t *__restrict__ src_id_off, const uint32_t *__restrict__ src_id_len, FwdPairsOut out,
+    uint32_t *__restrict__ dest_out)
 {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= n)
         return;
-    uint32_t lo = 0, hi = n_streams; // base[lo] <= p < base[hi]
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (base[mid] <= p)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const uint32_t s = lo, slot = p - base[s];
-    const uint32_t c0 = cidx[s], c = cidx[s + 1] - c0;
-    const uint32_t q = prepend ? slot >> 1 : slot;
-    const bool id_slot = prepend && !(slot & 1u);
-    uint32_t fl, len;
-    uint64_t off;
-    if (q < c) {
-        fl = carry_flags[c0 + q];
-        off = carry_off[c0 + q];
-        len = carry_len[c0 + q];
-    } else {
-        const uint64_t j = (uint64_t) s * max_frames + (q - c);
-        fl = flags_out[j];
-        off = plain_off[j];
-        len = frame_len[j] - 33u; // (a forwarded frame has status 0: a box and a flags byte)
-    }
-    const bool forwarded = q < fwd[s].held_first && !(fl & ZMQG_MSG_COMMAND);
+    const uint32_t s = fwd_stream_of(tab.base, src.n_streams, p);
+    const FwdSlot sl = fwd_slot(p - tab.base[s], prepend);
+    const FwdElem el = fwd_elem(src, s, sl.q);
+    const bool forwarded = sl.q < src.fwd[s].held_first && !(el.flags & ZMQG_MSG_COMMAND);
     // (head[] and rank[] are written for forwarded elements only)
-    const uint32_t e = ebase[s] + q;
+    const uint32_t e = tab.ebase[s] + sl.q;
     uint32_t dest = kFwdLbNone;
-    if (forwarded && (!id_slot || head[e] == q)) {
+    if (forwarded && (!sl.id_slot || head[e] == sl.q)) {
         dest = kFwdLbNoPeer;
         const uint32_t g = sgrp[s];
         if (g != kFwdLbNoGroup) {
@@ -177,16 +134,7 @@ __global__ __launch_bounds__(256) void k_fwd_pairs_lb(
                 dest = fwd_lb_pick(lb_dst, r, fwd_lb_at(first[s], rank[e], r.A), n_dst);
         }
     }
-    const bool live = dest < kFwdLbNoPeer;
-    if (id_slot) {
-        fl = ZMQG_MSG_MORE;
-        off = src_id_off[s];
-        len = src_id_len[s];
-    }
-    p_stream[p] = live ? dest : kZsendNoSession;
-    p_flags[p] = live ? (uint8_t) (fl & ZMQG_MSG_MORE) : 0;
-    p_off[p] = live ? off : 0;
-    p_len[p] = live ? len : 0u;
+    fwd_store_pair(out, p, dest < kFwdLbNoPeer, dest, sl.id_slot ? fwd_id_part(src_id_off, src_id_len, s) : el);
     if (dest_out)
         dest_out[p] = dest;
 }

@@ -27,13 +27,7 @@
 // `live`.  fwd_prefix_match, the compare of one prefix with all its range
 // checks, also compiles for the host (tests/host/test_fwd_match.cpp).
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define ZMQG_FWDM_FN __host__ __device__ inline
-#else
-#define ZMQG_FWDM_FN inline
-#endif
+#include "curve_fwd_common.hpp"
 
 namespace zmqg {
 
@@ -42,7 +36,7 @@ namespace zmqg {
 // read from `topic` itself.  A subscription that does not lie within
 // sub_bytes[0 .. sub_bytes_len) never matches and none of its bytes is read; no
 // byte at or past topic_len is read.
-ZMQG_FWDM_FN bool fwd_prefix_match(const uint8_t *win, uint32_t win_len, const uint8_t *topic, uint32_t topic_len,
+ZMQG_FWD_FN bool fwd_prefix_match(const uint8_t *win, uint32_t win_len, const uint8_t *topic, uint32_t topic_len,
                                    uint64_t off, uint32_t len, const uint8_t *sub_bytes, uint64_t sub_bytes_len)
 {
     if (len > topic_len)
@@ -79,7 +73,7 @@ ZMQG_FWDM_FN bool fwd_prefix_match(const uint8_t *win, uint32_t win_len, const u
 
 // destination t's subscriptions [lo, hi) of a table the host cannot validate:
 // entries above n_subs clamped to it, a falling pair an empty range
-ZMQG_FWDM_FN void fwd_sub_range(uint32_t idx_lo, uint32_t idx_hi, uint32_t n_subs, uint32_t &lo, uint32_t &hi)
+ZMQG_FWD_FN void fwd_sub_range(uint32_t idx_lo, uint32_t idx_hi, uint32_t n_subs, uint32_t &lo, uint32_t &hi)
 {
     lo = idx_lo < n_subs ? idx_lo : n_subs;
     hi = idx_hi < n_subs ? idx_hi : n_subs;
@@ -89,9 +83,7 @@ ZMQG_FWDM_FN void fwd_sub_range(uint32_t idx_lo, uint32_t idx_hi, uint32_t n_sub
 
 #if defined(__HIPCC__)
 
-constexpr uint32_t kFwdTopicWin = 256;   // bytes of a topic staged in LDS
 constexpr uint32_t kFwdMatchThreads = 256; // k_fwd_match: 4 waves, an element each
-constexpr uint32_t kFwdNoHead = 0xffffffffu;
 
 // the highest set bit of m at or below lane l, or -1
 __device__ __forceinline__ int fwd_top_at(uint64_t m, uint32_t l)
@@ -106,33 +98,27 @@ __device__ __forceinline__ int fwd_top_at(uint64_t m, uint32_t l)
 // give rank[ebase[s] + q], for forwarded data elements, the number of heads of
 // the stream before its message's head, and msgs[s], the stream's heads.
 template <bool kRank>
-__global__ __launch_bounds__(kFwdThreads) void k_fwd_heads(uint32_t n_streams, uint64_t max_frames,
-                                                          const uint32_t *__restrict__ cidx,
-                                                          const uint32_t *__restrict__ ebase,
-                                                          const uint8_t *__restrict__ carry_flags,
-                                                          const uint8_t *__restrict__ flags_out,
-                                                          const zmqg_forward_result *__restrict__ fwd,
-                                                          uint32_t *__restrict__ head, uint32_t *__restrict__ rank,
-                                                          uint32_t *__restrict__ msgs)
+__global__ __launch_bounds__(kFwdThreads) void k_fwd_heads(FwdSrc src, FwdTab tab, uint32_t *__restrict__ head,
+                                                          uint32_t *__restrict__ rank, uint32_t *__restrict__ msgs)
 {
     const uint32_t lane = threadIdx.x & 63u, s = blockIdx.x * (kFwdThreads / 64u) + (threadIdx.x >> 6);
-    if (s >= n_streams)
+    if (s >= src.n_streams)
         return; // (the whole wave)
-    const uint32_t e0 = ebase[s];
-    if (ebase[s + 1] == e0) { // no routes: no pairs read it
+    const uint32_t e0 = tab.ebase[s];
+    if (tab.ebase[s + 1] == e0) { // no routes: no pairs read it
         if (kRank && lane == 0)
             msgs[s] = 0;
         return;
     }
-    const uint32_t c0 = cidx[s], c = cidx[s + 1] - c0;
-    const uint64_t lim = fwd[s].held_first, slot0 = (uint64_t) s * max_frames; // (below F: every frame has status 0)
+    const uint32_t c0 = src.cidx[s], c = src.cidx[s + 1] - c0;
+    const uint64_t lim = src.fwd[s].held_first; // (below F: every frame has status 0)
     bool closed = true;          // the last data element before this step has MORE clear (or there is none)
     uint32_t last = kFwdNoHead;  // the last head before this step
     uint32_t before = 0;         // kRank: the heads before this step
     for (uint64_t q0 = 0; q0 < lim; q0 += 64u) {
         const uint64_t q = q0 + lane;
         const bool in = q < lim;
-        const uint32_t fl = in ? (q < c ? carry_flags[c0 + q] : flags_out[slot0 + (q - c)]) : 0u;
+        const uint32_t fl = in ? fwd_elem_flags(src, s, c0, c, q) : 0u;
         const bool part = in && !(fl & ZMQG_MSG_COMMAND);
         const uint64_t partm = __builtin_amdgcn_ballot_w64(part);
         const uint64_t lastm = __builtin_amdgcn_ballot_w64(part && !(fl & ZMQG_MSG_MORE));
@@ -161,13 +147,10 @@ __global__ __launch_bounds__(kFwdThreads) void k_fwd_heads(uint32_t n_streams, u
 // k_fwd_pairs searches base.  match[base[s] + q * d + k] = destination
 // rdst[ridx[s] + k] is subscribed to the topic of head q (negated with invert).
 __global__ __launch_bounds__(kFwdMatchThreads) void k_fwd_match(
-    uint32_t n_elems, uint32_t n_streams, uint64_t max_frames, const uint32_t *__restrict__ base,
-    const uint32_t *__restrict__ cidx, const uint32_t *__restrict__ ridx, const uint32_t *__restrict__ ebase,
-    const uint32_t *__restrict__ rdst, const uint64_t *__restrict__ carry_off, const uint32_t *__restrict__ carry_len,
-    const uint64_t *__restrict__ plain_off, const uint32_t *__restrict__ frame_len, const uint8_t *__restrict__ plain,
-    const zmqg_forward_result *__restrict__ fwd, const uint32_t *__restrict__ head, uint32_t n_subs,
-    const uint32_t *__restrict__ sub_idx, const uint64_t *__restrict__ sub_off, const uint32_t *__restrict__ sub_len,
-    const uint8_t *__restrict__ sub_bytes, uint64_t sub_bytes_len, uint32_t invert, uint8_t *__restrict__ match)
+    uint32_t n_elems, FwdSrc src, FwdTab tab, const uint8_t *__restrict__ plain, const uint32_t *__restrict__ head,
+    uint32_t n_subs, const uint32_t *__restrict__ sub_idx, const uint64_t *__restrict__ sub_off,
+    const uint32_t *__restrict__ sub_len, const uint8_t *__restrict__ sub_bytes, uint64_t sub_bytes_len,
+    uint32_t invert, uint8_t *__restrict__ match)
 {
     __shared__ uint8_t s_win[kFwdMatchThreads / 64u][kFwdTopicWin];
     __shared__ uint64_t s_start[kFwdMatchThreads / 64u][64]; // a round's routes: the first item of each,
@@ -177,35 +160,19 @@ __global__ __launch_bounds__(kFwdMatchThreads) void k_fwd_match(
     const uint32_t e = blockIdx.x * (kFwdMatchThreads / 64u) + w;
     if (e >= n_elems)
         return; // (the whole wave; no barrier below)
-    uint32_t lo = 0, hi = n_streams; // ebase[lo] <= e < ebase[hi]
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (ebase[mid] <= e)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const uint32_t s = lo, q = e - ebase[s];
-    if (q >= fwd[s].held_first || head[e] != q)
+    const uint32_t s = fwd_stream_of(tab.ebase, src.n_streams, e), q = e - tab.ebase[s];
+    if (q >= src.fwd[s].held_first || head[e] != q)
         return; // not forwarded, or no head
-    const uint32_t c0 = cidx[s], c = cidx[s + 1] - c0, r0 = ridx[s], d = ridx[s + 1] - r0;
-    uint64_t off;
-    uint32_t tlen;
-    if (q < c) {
-        off = carry_off[c0 + q];
-        tlen = carry_len[c0 + q];
-    } else {
-        const uint64_t j = (uint64_t) s * max_frames + (q - c);
-        off = plain_off[j];
-        tlen = frame_len[j] - 33u; // (a forwarded frame has status 0)
-    }
-    const uint8_t *topic = plain + off;
+    const uint32_t r0 = tab.ridx[s], d = tab.ridx[s + 1] - r0;
+    const FwdElem el = fwd_elem(src, s, q);
+    const uint32_t tlen = el.len;
+    const uint8_t *topic = plain + el.off;
     uint8_t *win = s_win[w];
     const uint32_t wlen = tlen < kFwdTopicWin ? tlen : kFwdTopicWin;
     for (uint32_t i = lane; i < wlen; i += 64u)
         win[i] = topic[i];
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // (the window is the wave's own: no barrier)
-    const uint64_t m0 = (uint64_t) base[s] + (uint64_t) q * d;
+    const uint64_t m0 = (uint64_t) tab.base[s] + (uint64_t) q * d;
     // 64 routes a round: lane l holds route kb + l's range of subscriptions;
     // the ranges laid end to end are the round's items, 64 of them a step
     uint64_t *start = s_start[w];
@@ -214,15 +181,10 @@ __global__ __launch_bounds__(kFwdMatchThreads) void k_fwd_match(
         const uint32_t k = kb + lane;
         uint32_t j0 = 0, j1 = 0;
         if (k < d) {
-            const uint32_t t = rdst[r0 + k];
+            const uint32_t t = tab.rdst[r0 + k];
             fwd_sub_range(sub_idx[t], sub_idx[t + 1], n_subs, j0, j1);
         }
-        uint64_t incl = j1 - j0; // the inclusive sum over the lanes (each at most 2^31 - 1)
-        for (uint32_t o = 1; o < 64u; o <<= 1) {
-            const uint64_t up = __shfl_up((unsigned long long) incl, o, 64);
-            if (lane >= o)
-                incl += up;
-        }
+        const uint64_t incl = wave_incl_sum_u64(j1 - j0, lane); // (each at most 2^31 - 1)
         const uint64_t total = __shfl((unsigned long long) incl, 63, 64);
         start[lane] = incl - (j1 - j0);
         first[lane] = j0;
@@ -231,14 +193,7 @@ __global__ __launch_bounds__(kFwdMatchThreads) void k_fwd_match(
         for (uint64_t it = 0; it < total; it += 64u) { // (uniform)
             const uint64_t item = it + lane;
             if (item < total) {
-                uint32_t a = 0, z = 64; // start[a] <= item < start[z]; a route without items shares its successor's
-                while (z - a > 1u) {
-                    const uint32_t mid = (a + z) / 2u;
-                    if (start[mid] <= item)
-                        a = mid;
-                    else
-                        z = mid;
-                }
+                const uint32_t a = fwd_stream_of(start, 64u, item); // (a route without items shares its successor's)
                 const uint32_t j = first[a] + (uint32_t) (item - start[a]);
                 if (fwd_prefix_match(win, kFwdTopicWin, topic, tlen, sub_off[j], sub_len[j], sub_bytes,
                                      sub_bytes_len))

@@ -24,20 +24,12 @@
 // fwd_route_lookup also compile for the host (tests/host/test_fwd_route.cpp);
 // only the search for the first differing byte has a wave-cooperative form.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define ZMQG_FWDR_FN __host__ __device__ inline
-#else
-#define ZMQG_FWDR_FN inline
-#endif
+#include "curve_fwd_common.hpp"
 
 namespace zmqg {
 
-constexpr uint32_t kFwdRouteNone = 0xffffffffu;      // ZMQG_ROUTE_NONE
-constexpr uint32_t kFwdRouteAddress = 0xfffffffeu;   // ZMQG_ROUTE_ADDRESS
-constexpr uint32_t kFwdRouteUnknown = 0xfffffffdu;   // ZMQG_ROUTE_UNKNOWN
-constexpr uint32_t kFwdRouteMalformed = 0xfffffffcu; // ZMQG_ROUTE_MALFORMED
+constexpr uint32_t kFwdRouteNone = ZMQG_ROUTE_NONE, kFwdRouteAddress = ZMQG_ROUTE_ADDRESS;
+constexpr uint32_t kFwdRouteUnknown = ZMQG_ROUTE_UNKNOWN, kFwdRouteMalformed = ZMQG_ROUTE_MALFORMED;
 
 // An address: win holds its first min(len, win_len) bytes (a staged copy);
 // bytes at or past win_len are read from p itself.
@@ -46,7 +38,7 @@ struct FwdAddr {
     uint32_t win_len;
     const uint8_t *p;
     uint32_t len;
-    ZMQG_FWDR_FN uint8_t at(uint64_t i) const { return i < win_len ? win[i] : p[i]; }
+    ZMQG_FWD_FN uint8_t at(uint64_t i) const { return i < win_len ? win[i] : p[i]; }
 };
 
 // Entry j of a table the host cannot validate.  An entry that does not lie
@@ -58,7 +50,7 @@ struct FwdId {
     bool is_void;
 };
 
-ZMQG_FWDR_FN FwdId fwd_id_view(uint64_t j, const uint64_t *id_off, const uint32_t *id_len, const uint8_t *id_bytes,
+ZMQG_FWD_FN FwdId fwd_id_view(uint64_t j, const uint64_t *id_off, const uint32_t *id_len, const uint8_t *id_bytes,
                                uint64_t id_bytes_len)
 {
     const uint64_t off = id_off[j];
@@ -73,7 +65,7 @@ ZMQG_FWDR_FN FwdId fwd_id_view(uint64_t j, const uint64_t *id_off, const uint32_
 // The index of the first byte among the first n at which id and the address
 // differ, or n: one byte after the other.
 struct FwdSerialDiff {
-    ZMQG_FWDR_FN uint64_t operator()(const uint8_t *id, const FwdAddr &a, uint64_t n) const
+    ZMQG_FWD_FN uint64_t operator()(const uint8_t *id, const FwdAddr &a, uint64_t n) const
     {
         uint64_t i = 0;
         while (i < n && id[i] == a.at(i))
@@ -84,14 +76,14 @@ struct FwdSerialDiff {
 
 // blob_t::operator< (src/blob.hpp:92): memcmp over the shorter length gives
 // < 0, or gives 0 and the entry is shorter.
-template <class Diff> ZMQG_FWDR_FN bool fwd_id_less(const FwdId &e, const FwdAddr &a, const Diff &diff)
+template <class Diff> ZMQG_FWD_FN bool fwd_id_less(const FwdId &e, const FwdAddr &a, const Diff &diff)
 {
     const uint64_t n = e.len < a.len ? e.len : a.len;
     const uint64_t d = diff(e.p, a, n);
     return d < n ? e.p[d] < a.at(d) : e.len < a.len;
 }
 
-template <class Diff> ZMQG_FWDR_FN bool fwd_id_equal(const FwdId &e, const FwdAddr &a, const Diff &diff)
+template <class Diff> ZMQG_FWD_FN bool fwd_id_equal(const FwdId &e, const FwdAddr &a, const Diff &diff)
 {
     return !e.is_void && e.len == a.len && diff(e.p, a, a.len) == a.len;
 }
@@ -101,7 +93,7 @@ template <class Diff> ZMQG_FWDR_FN bool fwd_id_equal(const FwdId &e, const FwdAd
 // a destination below n_dst.  Defined for any table; on one sorted by
 // fwd_id_less with distinct ids it is std::map::find.
 template <class Diff>
-ZMQG_FWDR_FN uint32_t fwd_route_lookup(const FwdAddr &a, uint64_t n_ids, const uint64_t *id_off,
+ZMQG_FWD_FN uint32_t fwd_route_lookup(const FwdAddr &a, uint64_t n_ids, const uint64_t *id_off,
                                        const uint32_t *id_len, const uint32_t *id_dst, const uint8_t *id_bytes,
                                        uint64_t id_bytes_len, uint64_t n_dst, const Diff &diff)
 {
@@ -122,8 +114,7 @@ ZMQG_FWDR_FN uint32_t fwd_route_lookup(const FwdAddr &a, uint64_t n_ids, const u
 #if defined(__HIPCC__)
 
 constexpr uint32_t kFwdRouteThreads = 256; // k_fwd_route: 4 waves, an element each
-constexpr uint32_t kFwdRouterPrepend = 1u; // ZMQG_ROUTER_PREPEND
-constexpr uint32_t kFwdRouterRoute = 2u;   // ZMQG_ROUTER_ROUTE
+constexpr uint32_t kFwdRouterPrepend = ZMQG_ROUTER_PREPEND, kFwdRouterRoute = ZMQG_ROUTER_ROUTE;
 
 // FwdSerialDiff with the wave's lanes over the bytes, 64 a step (every lane
 // calls it with the same arguments and gets the same answer)
@@ -148,49 +139,22 @@ struct FwdWaveDiff {
 // whole message.  The address is the head's payload, or with prepend the
 // stream's own id (MORE set by definition: never malformed).
 __global__ __launch_bounds__(kFwdRouteThreads) void k_fwd_route(
-    uint32_t n_elems, uint32_t n_streams, uint64_t max_frames, const uint32_t *__restrict__ cidx,
-    const uint32_t *__restrict__ ebase, const uint64_t *__restrict__ carry_off, const uint32_t *__restrict__ carry_len,
-    const uint8_t *__restrict__ carry_flags, const uint64_t *__restrict__ plain_off,
-    const uint32_t *__restrict__ frame_len, const uint8_t *__restrict__ flags_out, const uint8_t *__restrict__ plain,
-    const zmqg_forward_result *__restrict__ fwd, const uint32_t *__restrict__ head, uint32_t prepend,
-    const uint64_t *__restrict__ src_id_off, const uint32_t *__restrict__ src_id_len, uint64_t n_ids,
-    const uint64_t *__restrict__ id_off, const uint32_t *__restrict__ id_len, const uint32_t *__restrict__ id_dst,
-    const uint8_t *__restrict__ id_bytes, uint64_t id_bytes_len, uint64_t n_dst, uint32_t *__restrict__ verdict)
+    uint32_t n_elems, FwdSrc src, FwdTab tab, const uint8_t *__restrict__ plain,
+    const uint32_t *__restrict__ head, uint32_t prepend, const uint64_t *__restrict__ src_id_off,
+    const uint32_t *__restrict__ src_id_len, uint64_t n_ids, const uint64_t *__restrict__ id_off,
+    const uint32_t *__restrict__ id_len, const uint32_t *__restrict__ id_dst, const uint8_t *__restrict__ id_bytes,
+    uint64_t id_bytes_len, uint64_t n_dst, uint32_t *__restrict__ verdict)
 {
     __shared__ uint8_t s_win[kFwdRouteThreads / 64u][kFwdTopicWin];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t e = blockIdx.x * (kFwdRouteThreads / 64u) + w;
     if (e >= n_elems)
         return; // (the whole wave; no barrier below)
-    uint32_t lo = 0, hi = n_streams; // ebase[lo] <= e < ebase[hi]
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (ebase[mid] <= e)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const uint32_t s = lo, q = e - ebase[s];
-    if (q >= fwd[s].held_first || head[e] != q)
+    const uint32_t s = fwd_stream_of(tab.ebase, src.n_streams, e), q = e - tab.ebase[s];
+    if (q >= src.fwd[s].held_first || head[e] != q)
         return; // not forwarded, or no head
-    const uint32_t c0 = cidx[s], c = cidx[s + 1] - c0;
-    uint64_t off;
-    uint32_t alen, fl;
-    if (prepend) {
-        off = src_id_off[s];
-        alen = src_id_len[s];
-        fl = ZMQG_MSG_MORE;
-    } else if (q < c) {
-        off = carry_off[c0 + q];
-        alen = carry_len[c0 + q];
-        fl = carry_flags[c0 + q];
-    } else {
-        const uint64_t j = (uint64_t) s * max_frames + (q - c);
-        off = plain_off[j];
-        alen = frame_len[j] - 33u; // (a forwarded frame has status 0)
-        fl = flags_out[j];
-    }
-    if (!(fl & ZMQG_MSG_MORE)) { // an address that is the whole message: src/router.cpp:168-171, :207-211
+    const FwdElem el = prepend ? fwd_id_part(src_id_off, src_id_len, s) : fwd_elem(src, s, q);
+    if (!(el.flags & ZMQG_MSG_MORE)) { // an address that is the whole message: src/router.cpp:168-171, :207-211
         if (lane == 0)
             verdict[e] = kFwdRouteMalformed;
         return;
@@ -198,9 +162,9 @@ __global__ __launch_bounds__(kFwdRouteThreads) void k_fwd_route(
     uint8_t *win = s_win[w];
     FwdAddr a;
     a.win = win;
-    a.win_len = alen < kFwdTopicWin ? alen : kFwdTopicWin;
-    a.p = plain + off;
-    a.len = alen;
+    a.win_len = el.len < kFwdTopicWin ? el.len : kFwdTopicWin;
+    a.p = plain + el.off;
+    a.len = el.len;
     for (uint32_t i = lane; i < a.win_len; i += 64u)
         win[i] = a.p[i];
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // (the window is the wave's own: no barrier)
@@ -210,75 +174,41 @@ __global__ __launch_bounds__(kFwdRouteThreads) void k_fwd_route(
         verdict[e] = t;
 }
 
-// One lane per pair of the router pair space: stream s owns m * (c(s) +
-// max_frames) * d'(s) pairs, p = base(s) + slot * d'(s) + k.  m = 2 with
-// prepend alone (slot 2q + 1 is element q, slot 2q the id part in front of it),
-// else 1; d' = 1 with route (ridx / rdst are not read), else the stream's routes.
+// One lane per pair; prepend alone has id slots, route one route slot a stream
+// (curve_fwd_common.hpp).  Destination rule: without route the pair's route, an id part only in front of
+// a head; with route the verdict of the message's head, the address part itself
+// consumed unless the id part stands for it (prepend).
 __global__ __launch_bounds__(256) void k_fwd_pairs_router(
-    uint32_t n, uint32_t n_streams, uint64_t max_frames, uint32_t rflags, const uint32_t *__restrict__ base,
-    const uint32_t *__restrict__ cidx, const uint32_t *__restrict__ ridx, const uint32_t *__restrict__ rdst,
-    const uint32_t *__restrict__ ebase, const uint64_t *__restrict__ carry_off, const uint32_t *__restrict__ carry_len,
-    const uint8_t *__restrict__ carry_flags, const uint64_t *__restrict__ plain_off,
-    const uint32_t *__restrict__ frame_len, const uint8_t *__restrict__ flags_out,
-    const zmqg_forward_result *__restrict__ fwd, const uint32_t *__restrict__ head,
+    uint32_t n, FwdSrc src, FwdTab tab, uint32_t rflags, const uint32_t *__restrict__ head,
     const uint32_t *__restrict__ verdict, const uint64_t *__restrict__ src_id_off,
-    const uint32_t *__restrict__ src_id_len, uint32_t *__restrict__ p_stream, uint8_t *__restrict__ p_flags,
-    uint64_t *__restrict__ p_off, uint32_t *__restrict__ p_len, uint32_t *__restrict__ dest_out)
+    const uint32_t *__restrict__ src_id_len, FwdPairsOut out, uint32_t *__restrict__ dest_out)
 {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= n)
         return;
-    uint32_t lo = 0, hi = n_streams; // base[lo] <= p < base[hi]
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (base[mid] <= p)
-            lo = mid;
-        else
-            hi = mid;
-    }
+    const uint32_t s = fwd_stream_of(tab.base, src.n_streams, p);
     const bool route = rflags & kFwdRouterRoute, prepend = rflags & kFwdRouterPrepend;
-    const bool twice = prepend && !route;
-    const uint32_t s = lo, r0 = route ? 0u : ridx[s], d = route ? 1u : ridx[s + 1] - r0; // (d > 0: the stream has pairs)
-    const uint32_t c0 = cidx[s], c = cidx[s + 1] - c0;
-    const uint32_t r = p - base[s], slot = r / d, k = r - slot * d;
-    const uint32_t q = twice ? slot >> 1 : slot;
-    const bool id_slot = twice && !(slot & 1u);
-    uint32_t fl, len;
-    uint64_t off;
-    if (q < c) {
-        fl = carry_flags[c0 + q];
-        off = carry_off[c0 + q];
-        len = carry_len[c0 + q];
-    } else {
-        const uint64_t j = (uint64_t) s * max_frames + (q - c);
-        fl = flags_out[j];
-        off = plain_off[j];
-        len = frame_len[j] - 33u; // (a forwarded frame has status 0: a box and a flags byte)
-    }
-    const bool forwarded = q < fwd[s].held_first && !(fl & ZMQG_MSG_COMMAND);
+    // (d > 0: the stream has pairs)
+    const uint32_t r0 = route ? 0u : tab.ridx[s], d = route ? 1u : tab.ridx[s + 1] - r0;
+    const uint32_t r = p - tab.base[s], slot = r / d, k = r - slot * d;
+    const FwdSlot sl = fwd_slot(slot, prepend && !route);
+    const FwdElem el = fwd_elem(src, s, sl.q);
+    const bool forwarded = sl.q < src.fwd[s].held_first && !(el.flags & ZMQG_MSG_COMMAND);
     // (head[] is written for forwarded elements, verdict[] for their heads only)
-    const uint32_t h = forwarded ? head[ebase[s] + q] : kFwdNoHead;
+    const uint32_t h = forwarded ? head[tab.ebase[s] + sl.q] : kFwdNoHead;
     uint32_t dest = kFwdRouteNone;
     if (forwarded && !route) {
-        if (!id_slot || h == q)
-            dest = rdst[r0 + k];
+        if (!sl.id_slot || h == sl.q)
+            dest = tab.rdst[r0 + k];
     } else if (forwarded) {
-        const uint32_t v = verdict[ebase[s] + h];
-        if (!prepend && h == q) // the address part: consumed
+        const uint32_t v = verdict[tab.ebase[s] + h];
+        if (!prepend && h == sl.q) // the address part: consumed
             dest = v == kFwdRouteMalformed ? kFwdRouteMalformed : kFwdRouteAddress;
         else
             dest = v;
     }
-    const bool live = dest < kFwdRouteMalformed;
-    if (id_slot) {
-        fl = ZMQG_MSG_MORE;
-        off = src_id_off[s];
-        len = src_id_len[s];
-    }
-    p_stream[p] = live ? dest : kZsendNoSession;
-    p_flags[p] = live ? (uint8_t) (fl & ZMQG_MSG_MORE) : 0;
-    p_off[p] = live ? off : 0;
-    p_len[p] = live ? len : 0u;
+    fwd_store_pair(out, p, dest < kFwdRouteMalformed, dest,
+                   sl.id_slot ? fwd_id_part(src_id_off, src_id_len, s) : el);
     if (dest_out)
         dest_out[p] = dest;
 }

@@ -1823,11 +1823,6 @@ uint32_t body_grid(const zmqg_ctx *ctx)
     return kBodyWgPerCu * (ctx->cus > 0 ? (uint32_t) ctx->cus : 256u);
 }
 
-int check_n(uint64_t n)
-{
-    return n > 0x7fffffffull ? -EINVAL : 0;
-}
-
 hipEvent_t pool_event(zmqg_ctx *ctx)
 {
     if (!ctx->event_pool.empty()) {
@@ -3239,18 +3234,9 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
         z.g_cap = cap;
     }
     // candidates: signatures are >= 8 bytes apart, one candidate each
-    const uint64_t ccap = in_bytes / 8 + 2;
-    if (ccap > z.c_cap) {
-        const uint64_t cap = grown_cap(z.c_cap, 1024, ccap);
-        z.c_cap = 0;
-        ZRESERVE(ctx, z.cand, cap, st);
-        ZRESERVE(ctx, z.nb, cap, st);
-        ZRESERVE(ctx, z.wid, cap, st);
-        ZRESERVE(ctx, z.cdesc, cap, st);
-        ZRESERVE(ctx, z.cflag, cap, st);
-        z.c_cap = cap;
-    }
-    if ((rc = zmtp_frame_cap(ctx, max_frames, st)))
+    if ((rc = reserve_group(ctx, st, "cand..cflag", z.c_cap, 1024, in_bytes / 8 + 2, z.cand, z.nb, z.wid, z.cdesc,
+                            z.cflag)) ||
+        (rc = zmtp_frame_cap(ctx, max_frames, st)))
         return rc;
     ZRESERVE(ctx, z.walk, 1, st);
     const uint32_t g = (uint32_t) nwg;
@@ -3296,16 +3282,12 @@ int zmqg_decode_zmtp_async(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint6
                        (unsigned long long *) ((char *) z.walk.p + offsetof(ZmtpWalk, out_bytes)));
     ZCHECK(ctx, hipGetLastError());
     // the decode over max_frames (the empty frames fail as malformed and
-    // write nothing else); a maxmsgsize within the frame kernel's range bounds
-    // every frame, so the large-frame launches are skipped
-    zmqg_batch_opts o{};
-    o.size = sizeof o;
-    if (max_msg_size >= 0 && (uint64_t) max_msg_size <= kMaxFrameStream)
-        o.max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
+    // write nothing else), bounded by maxmsgsize where that helps
+    zmqg_batch_opts o;
     // (the frames' MORE / COMMAND bits ORed into flags_out, and the call's
     // result copied from the parse state, by the decode's frame kernel)
     return decode_batch_impl(ctx, max_frames, z.sid_fill, frame_in_off, frame_len, in, out_off, out, flags_out,
-                             status_out, o.max_len ? &o : nullptr, z.fflags, z.walk, result, stream);
+                             status_out, decode_len_bound(max_msg_size, &o), z.fflags, z.walk, result, stream);
 }
 
 // zmqg_decode_zmtp_multi behind its argument checks, n_streams and max_frames
@@ -3332,14 +3314,10 @@ static int decode_zmtp_multi_locked(zmqg_ctx *ctx, uint64_t n_streams, const uin
                        z.sid_fill, z.fflags, results);
     ZCHECK(ctx, hipGetLastError());
     // the decode over every slot (as zmqg_decode_zmtp_async: the empty frames
-    // fail as malformed; a maxmsgsize within the frame kernel's range skips
-    // the large-frame launches); the results are already in place
-    zmqg_batch_opts o{};
-    o.size = sizeof o;
-    if (max_msg_size >= 0 && (uint64_t) max_msg_size <= kMaxFrameStream)
-        o.max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
+    // fail as malformed); the results are already in place
+    zmqg_batch_opts o;
     return decode_batch_impl(ctx, slots, z.sid_fill, frame_in_off, frame_len, in, out_off, out, flags_out, status_out,
-                             o.max_len ? &o : nullptr, z.fflags, nullptr, nullptr, stream);
+                             decode_len_bound(max_msg_size, &o), z.fflags, nullptr, nullptr, stream);
 }
 
 int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
@@ -3365,296 +3343,16 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
                                     frame_in_off, frame_len, out_off, out, flags_out, status_out, results, stream);
 }
 
-// The receive side as zmqg_decode_zmtp_multi runs it, the plan (curve_forward.hpp)
-// and the send side as zmqg_encode_zmtp_multi runs it over the pairs, queued
-// back to back on `stream` under one hold of ctx->mu.
-// With `subs` (zmqg_forward_zmtp_sub_multi, its table checked by the caller) the
-// plan also finds every element's head and matches each head's topic against
-// its routes' subscriptions (curve_fwd_match.hpp): two launches more, and a
-// fourth row in the table.  Without it, zmqg_forward_zmtp_multi's launches.
-// With `rt` (zmqg_forward_zmtp_router_multi with a flag set, its own fields
-// checked by the caller; never together with subs) the pairs are the router pair
-// space (curve_fwd_route.hpp): the heads, with ROUTE the lookup of every head's
-// address, and the router's own pairs kernel in place of k_fwd_pairs.
-// With `lb` (zmqg_forward_zmtp_lb_multi, its own fields checked by the caller;
-// never together with subs or rt) every stream has one route slot, the table
-// also carries stream_group and the group-to-streams lists, and the plan is the
-// heads with the messages' ranks, the groups and the load balancer's own pairs
-// kernel (curve_fwd_lb.hpp).
-static int forward_multi_impl(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
-                              const zmqg_forward_router *rt, const zmqg_forward_lb *lb, void *stream)
-{
-    static_assert(kFwdLbNone == ZMQG_LB_NONE && kFwdLbNoPeer == ZMQG_LB_NO_PEER &&
-                      kFwdLbNoGroup == ZMQG_LB_NO_GROUP && kFwdLbPrepend == ZMQG_LB_PREPEND,
-                  "curve_fwd_lb.hpp restates the header's values");
-    static_assert(kFwdRouteNone == ZMQG_ROUTE_NONE && kFwdRouteAddress == ZMQG_ROUTE_ADDRESS &&
-                      kFwdRouteUnknown == ZMQG_ROUTE_UNKNOWN && kFwdRouteMalformed == ZMQG_ROUTE_MALFORMED &&
-                      kFwdRouterPrepend == ZMQG_ROUTER_PREPEND && kFwdRouterRoute == ZMQG_ROUTER_ROUTE,
-                  "curve_fwd_route.hpp restates the header's values");
-    // route: one route slot a stream, route_idx / route_dst not read (ROUTE, or the load balancer)
-    const bool route = (rt && (rt->flags & ZMQG_ROUTER_ROUTE)) || lb;
-    const bool prepend = (rt && (rt->flags & ZMQG_ROUTER_PREPEND)) || (lb && (lb->flags & ZMQG_LB_PREPEND));
-    const uint64_t slots_m = prepend && (lb || !route) ? 2u : 1u; // m: an id slot in front of every element
-    if (!ctx || !args || args->size != sizeof *args || args->reserved != 0)
-        return -EINVAL;
-    const zmqg_forward_zmtp &a = *args;
-    const uint64_t S = a.n_streams, MF = a.max_frames;
-    // the two underlying calls' own cases
-    if (!a.results || check_n(S) || check_n(MF) || check_n(S * MF))
-        return -EINVAL;
-    if (a.n_dst > kZsendMaxStreams || ctx->max_sessions > kReplayMaxSessions)
-        return -EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    ZCHECK(ctx, hipSetDevice(ctx->device));
-    if (S == 0)
-        return 0;
-    if (MF > 0 && (!a.stream_sid || !a.stream_off || !a.stream_len || !a.in || !a.frame_in_off || !a.frame_len ||
-                   !a.plain_off || !a.plain || !a.flags_out || !a.status_out))
-        return -EINVAL;
-    if ((!route && (!a.route_idx || a.route_idx[0] != 0)) || (a.carry_idx && a.carry_idx[0] != 0) || !a.pair_off ||
-        !a.fwd)
-        return -EINVAL;
-    if (a.n_dst > 0 && (!a.dst_sid || !a.dst_results))
-        return -EINVAL;
-    // N = the pairs: every element a stream can have, times its routes
-    uint64_t N = 0;
-    for (uint64_t s = 0; s < S; ++s) {
-        if ((!route && a.route_idx[s + 1] < a.route_idx[s]) || (a.carry_idx && a.carry_idx[s + 1] < a.carry_idx[s]))
-            return -EINVAL;
-        const uint64_t d = route ? 1u : a.route_idx[s + 1] - a.route_idx[s];
-        const uint64_t q = slots_m * ((a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u) + MF); // (below 2^34)
-        if (d && q > 0x7fffffffull / d)
-            return -EINVAL;
-        N += q * d;
-        if (check_n(N))
-            return -EINVAL;
-    }
-    const uint32_t R = route ? 0u : a.route_idx[S], CN = a.carry_idx ? a.carry_idx[S] : 0u;
-    if (R > 0 && !a.route_dst)
-        return -EINVAL;
-    for (uint32_t i = 0; i < R; ++i)
-        if (a.route_dst[i] >= a.n_dst)
-            return -EINVAL;
-    if (CN > 0 && (!a.carry_off || !a.carry_len || !a.carry_flags))
-        return -EINVAL;
-    if (N > 0 && (!a.plain || !a.out))
-        return -EINVAL;
-    if (route && N > 0 && a.n_dst == 0) // (the send side's own case: frames and no streams; routes cannot name none)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ZmtpWs &z = ctx->zw;
-    int rc;
-    if ((rc = order_after_last(ctx, st)))
-        return rc;
-    // the host arrays, copied before the call returns: the pinned staging, then
-    // one copy to the device, where every pair searches them
-    // (with subs a fourth row: ebase, each routed stream's first element among
-    // the elements of the routed streams -- at most N of them)
-    // (with lb behind them: stream_group [S], then the streams of every group,
-    // rising within a group, as an index [n_groups + 1] and a list [SG])
-    const uint64_t G = lb ? lb->n_groups : 0u;
-    uint64_t SG = 0; // the streams that have a group
-    for (uint64_t s = 0; lb && s < S; ++s)
-        SG += lb->stream_group[s] != ZMQG_LB_NO_GROUP;
-    const size_t rows = subs || rt || lb ? 4 : 3,
-                 words = rows * (size_t) (S + 1) + R + (lb ? (size_t) S + (size_t) (G + 1) + (size_t) SG : 0u);
-    if ((rc = sinst_room(ctx, 4 * words)))
-        return rc;
-    uint32_t *h_base = (uint32_t *) ctx->sinst, *h_cidx = h_base + (S + 1), *h_ridx = h_cidx + (S + 1),
-             *h_ebase = h_ridx + (S + 1), *h_rdst = h_base + rows * (S + 1);
-    if (lb) {
-        uint32_t *h_sgrp = h_rdst, *h_gidx = h_sgrp + S, *h_gstr = h_gidx + (G + 1);
-        memcpy(h_sgrp, lb->stream_group, 4 * (size_t) S);
-        memset(h_gidx, 0, 4 * (size_t) (G + 1));
-        for (uint64_t s = 0; s < S; ++s) // counts, one slot up
-            if (h_sgrp[s] != ZMQG_LB_NO_GROUP && h_sgrp[s] + 1u < G)
-                ++h_gidx[h_sgrp[s] + 2u];
-        for (uint64_t g = 2; g <= G; ++g) // h_gidx[g + 1] = the first stream of group g
-            h_gidx[g] += h_gidx[g - 1];
-        for (uint64_t s = 0; s < S; ++s) // h_gidx[g + 1] walks up to the end of group g
-            if (h_sgrp[s] != ZMQG_LB_NO_GROUP)
-                h_gstr[h_gidx[h_sgrp[s] + 1u]++] = (uint32_t) s;
-    }
-    uint32_t b = 0, eb = 0;
-    for (uint64_t s = 0; s <= S; ++s) {
-        h_base[s] = b;
-        h_cidx[s] = a.carry_idx ? a.carry_idx[s] : 0u;
-        h_ridx[s] = route ? (uint32_t) s : a.route_idx[s]; // (ROUTE: d'(s) = 1)
-        if (rows == 4)
-            h_ebase[s] = eb;
-        if (s < S) {
-            const uint64_t c = a.carry_idx ? a.carry_idx[s + 1] - a.carry_idx[s] : 0u;
-            const uint32_t ds = route ? 1u : a.route_idx[s + 1] - a.route_idx[s];
-            b += (uint32_t) (slots_m * (c + MF) * ds); // (N <= 2^31 - 1, checked above)
-            if (ds)
-                eb += (uint32_t) (c + MF);
-        }
-    }
-    const uint64_t EN = eb;
-    if (R)
-        memcpy(h_rdst, a.route_dst, 4 * (size_t) R);
-    ZRESERVE(ctx, z.p_tab, grown_cap(z.p_tab.count, 1024, words), st);
-    ZCHECK(ctx, hipMemcpyAsync(z.p_tab, ctx->sinst, 4 * words, hipMemcpyHostToDevice, st));
-    ZCHECK(ctx, hipEventRecord(ctx->sinst_done, st));
-    if (N > z.p_cap) {
-        const uint64_t cap = grown_cap(z.p_cap, 1024, N);
-        z.p_cap = 0;
-        ZRESERVE(ctx, z.p_stream, cap, st);
-        ZRESERVE(ctx, z.p_flags, cap, st);
-        ZRESERVE(ctx, z.p_off, cap, st);
-        ZRESERVE(ctx, z.p_len, cap, st);
-        z.p_cap = cap;
-    }
-    if (subs && N > z.m_cap) {
-        const uint64_t cap = grown_cap(z.m_cap, 1024, N);
-        z.m_cap = 0;
-        ZRESERVE(ctx, z.p_match, cap, st);
-        z.m_cap = cap;
-    }
-    if (lb && EN > z.l_cap) {
-        const uint64_t cap = grown_cap(z.l_cap, 1024, EN);
-        z.l_cap = 0;
-        ZRESERVE(ctx, z.e_rank, cap, st);
-        z.l_cap = cap;
-    }
-    if (lb && S > z.ls_cap) {
-        const uint64_t cap = grown_cap(z.ls_cap, 1024, S);
-        z.ls_cap = 0;
-        ZRESERVE(ctx, z.s_msgs, cap, st);
-        ZRESERVE(ctx, z.s_first, cap, st);
-        z.ls_cap = cap;
-    }
-    if ((subs || rt || lb) && EN > z.e_cap) {
-        const uint64_t cap = grown_cap(z.e_cap, 1024, EN);
-        z.e_cap = 0;
-        ZRESERVE(ctx, z.e_head, cap, st);
-        z.e_cap = cap;
-    }
-    if (route && !lb && EN > z.v_cap) {
-        const uint64_t cap = grown_cap(z.v_cap, 1024, EN);
-        z.v_cap = 0;
-        ZRESERVE(ctx, z.e_verdict, cap, st);
-        z.v_cap = cap;
-    }
-    // 1. the receive side
-    if (MF == 0)
-        ZCHECK(ctx, hipMemsetAsync(a.results, 0, S * sizeof *a.results, st));
-    else if ((rc = decode_zmtp_multi_locked(ctx, S, a.stream_sid, a.stream_off, a.stream_len, a.in, a.max_msg_size, MF,
-                                            a.frame_in_off, a.frame_len, a.plain_off, a.plain, a.flags_out,
-                                            a.status_out, a.results, stream)))
-        return rc;
-    // 2. the plan: what each stream forwards, then the encode's frame per pair
-    const uint32_t *d_base = z.p_tab, *d_cidx = d_base + (S + 1), *d_ridx = d_cidx + (S + 1),
-                   *d_ebase = d_ridx + (S + 1), *d_rdst = d_base + rows * (S + 1);
-    hipLaunchKernelGGL(k_fwd_scan, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
-                       dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, a.carry_flags,
-                       (const uint8_t *) a.flags_out, (const int32_t *) a.status_out,
-                       (const zmqg_zmtp_result *) a.results, a.fwd);
-    ZCHECK(ctx, hipGetLastError());
-    if (N > 0 && subs) {
-        // the heads (one wave per source stream), then each head's topic against
-        // its routes' subscriptions (one wave per element; N > 0: EN > 0)
-        hipLaunchKernelGGL(k_fwd_heads<false>, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
-                           dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
-                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p,
-                           (uint32_t *) nullptr, (uint32_t *) nullptr);
-        ZCHECK(ctx, hipGetLastError());
-        const uint64_t per = kFwdMatchThreads / 64u;
-        hipLaunchKernelGGL(k_fwd_match, dim3((unsigned) ((EN + per - 1) / per)), dim3(kFwdMatchThreads), 0, st,
-                           (uint32_t) EN, (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_ebase, d_rdst, a.carry_off,
-                           a.carry_len, (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
-                           (const uint8_t *) a.plain, (const zmqg_forward_result *) a.fwd,
-                           (const uint32_t *) z.e_head.p, (uint32_t) subs->n_subs, subs->sub_idx, subs->sub_off,
-                           subs->sub_len, subs->sub_bytes, subs->sub_bytes_len, subs->flags & ZMQG_SUBS_INVERT,
-                           z.p_match.p);
-        ZCHECK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_fwd_pairs<true>, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
-                           (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_rdst, a.carry_off, a.carry_len, a.carry_flags,
-                           (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
-                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.p_stream.p,
-                           z.p_flags.p, z.p_off.p, z.p_len.p, d_ebase, (const uint32_t *) z.e_head.p,
-                           (const uint8_t *) z.p_match.p, subs->match_out);
-        ZCHECK(ctx, hipGetLastError());
-    } else if (lb) {
-        // the heads with the rank of every message within its stream, every
-        // stream's ring position and every group's new cursor, the pairs (one
-        // wave per source stream; one wave per group; one lane per pair).
-        // Without pairs the groups alone, which then only clamp the cursors.
-        const uint32_t *d_sgrp = d_rdst, *d_gidx = d_sgrp + S, *d_gstr = d_gidx + (G + 1);
-        if (N > 0) {
-            hipLaunchKernelGGL(k_fwd_heads<true>, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
-                               dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
-                               (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p,
-                               z.e_rank.p, z.s_msgs.p);
-            ZCHECK(ctx, hipGetLastError());
-        }
-        if (G > 0) {
-            hipLaunchKernelGGL(k_fwd_lb_groups, dim3((unsigned) ((G + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
-                               dim3(kFwdThreads), 0, st, (uint32_t) G, d_gidx, d_gstr,
-                               N > 0 ? (const uint32_t *) z.s_msgs.p : (const uint32_t *) nullptr, lb->grp_idx,
-                               (uint32_t) lb->n_lb, lb->lb_cur, z.s_first.p);
-            ZCHECK(ctx, hipGetLastError());
-        }
-        if (N > 0) {
-            hipLaunchKernelGGL(k_fwd_pairs_lb, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
-                               (uint32_t) S, MF, lb->flags & ZMQG_LB_PREPEND, d_base, d_cidx, d_ebase, d_sgrp,
-                               a.carry_off, a.carry_len, a.carry_flags, (const uint64_t *) a.plain_off,
-                               (const uint32_t *) a.frame_len, (const uint8_t *) a.flags_out,
-                               (const zmqg_forward_result *) a.fwd, (const uint32_t *) z.e_head.p,
-                               (const uint32_t *) z.e_rank.p, (const uint32_t *) z.s_first.p, lb->grp_idx,
-                               (uint32_t) lb->n_lb, lb->lb_dst, a.n_dst, lb->src_id_off, lb->src_id_len, z.p_stream.p,
-                               z.p_flags.p, z.p_off.p, z.p_len.p, lb->dest_out);
-            ZCHECK(ctx, hipGetLastError());
-        }
-    } else if (N > 0 && rt) {
-        // the heads; with ROUTE the lookup of every head's address (one wave per
-        // element; N > 0: EN > 0); the router pair space
-        hipLaunchKernelGGL(k_fwd_heads<false>, dim3((unsigned) ((S + kFwdThreads / 64u - 1) / (kFwdThreads / 64u))),
-                           dim3(kFwdThreads), 0, st, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_flags,
-                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.e_head.p,
-                           (uint32_t *) nullptr, (uint32_t *) nullptr);
-        ZCHECK(ctx, hipGetLastError());
-        if (route) {
-            const uint64_t per = kFwdRouteThreads / 64u;
-            hipLaunchKernelGGL(k_fwd_route, dim3((unsigned) ((EN + per - 1) / per)), dim3(kFwdRouteThreads), 0, st,
-                               (uint32_t) EN, (uint32_t) S, MF, d_cidx, d_ebase, a.carry_off, a.carry_len,
-                               a.carry_flags, (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
-                               (const uint8_t *) a.flags_out, (const uint8_t *) a.plain,
-                               (const zmqg_forward_result *) a.fwd, (const uint32_t *) z.e_head.p,
-                               (uint32_t) prepend, rt->src_id_off, rt->src_id_len, rt->n_ids, rt->id_off, rt->id_len,
-                               rt->id_dst, rt->id_bytes, rt->id_bytes_len, a.n_dst, z.e_verdict.p);
-            ZCHECK(ctx, hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_fwd_pairs_router, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
-                           (uint32_t) S, MF, rt->flags, d_base, d_cidx, d_ridx, d_rdst, d_ebase, a.carry_off,
-                           a.carry_len, a.carry_flags, (const uint64_t *) a.plain_off,
-                           (const uint32_t *) a.frame_len, (const uint8_t *) a.flags_out,
-                           (const zmqg_forward_result *) a.fwd, (const uint32_t *) z.e_head.p,
-                           (const uint32_t *) z.e_verdict.p, rt->src_id_off, rt->src_id_len, z.p_stream.p,
-                           z.p_flags.p, z.p_off.p, z.p_len.p, rt->dest_out);
-        ZCHECK(ctx, hipGetLastError());
-    } else if (N > 0) {
-        hipLaunchKernelGGL(k_fwd_pairs<false>, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, st, (uint32_t) N,
-                           (uint32_t) S, MF, d_base, d_cidx, d_ridx, d_rdst, a.carry_off, a.carry_len, a.carry_flags,
-                           (const uint64_t *) a.plain_off, (const uint32_t *) a.frame_len,
-                           (const uint8_t *) a.flags_out, (const zmqg_forward_result *) a.fwd, z.p_stream.p,
-                           z.p_flags.p, z.p_off.p, z.p_len.p, (const uint32_t *) nullptr, (const uint32_t *) nullptr,
-                           (const uint8_t *) nullptr, (uint8_t *) nullptr);
-        ZCHECK(ctx, hipGetLastError());
-    }
-    // 3. the send side: the pairs are its frames, the destinations its streams
-    if (a.n_dst == 0) {
-        ZCHECK(ctx, hipMemsetAsync(a.pair_off, 0, sizeof(uint64_t), st));
-        return 0;
-    }
-    return encode_multi_locked<kZsendZmtp>(ctx, a.n_dst, a.dst_sid, N, z.p_stream, nullptr, z.p_flags, z.p_off,
-                                           z.p_len, a.plain, nullptr, a.out, a.out_bytes, a.pair_off, a.pair_status,
-                                           a.dst_results, stream);
-}
+#include "curve_fwd_host.hpp" // forward_begin, fwd_plan_*, forward_finish
 
 int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
 {
-    return forward_multi_impl(ctx, args, nullptr, nullptr, nullptr, stream);
+    const FwdTableIn in = {args, false, false, 1u, nullptr, 0};
+    FwdCall c;
+    int rc;
+    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_static(ctx, c)))
+        return rc;
+    return forward_finish(ctx, c);
 }
 
 // The table's launch-free checks; what the host cannot see (sub_idx's entries,
@@ -3667,7 +3365,12 @@ int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, co
     if (check_n(subs->n_subs) || (args->n_dst > 0 && !subs->sub_idx) ||
         (subs->n_subs > 0 && (!subs->sub_off || !subs->sub_len)) || (subs->sub_bytes_len > 0 && !subs->sub_bytes))
         return -EINVAL;
-    return forward_multi_impl(ctx, args, subs, nullptr, nullptr, stream);
+    const FwdTableIn in = {args, false, true, 1u, nullptr, 0};
+    FwdCall c;
+    int rc;
+    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_sub(ctx, c, *subs)))
+        return rc;
+    return forward_finish(ctx, c);
 }
 
 // The router struct's launch-free checks; the id table's contents the lookup
@@ -3678,13 +3381,22 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
     if (!ctx || !args || !router || router->size != sizeof *router ||
         (router->flags & ~(ZMQG_ROUTER_PREPEND | ZMQG_ROUTER_ROUTE)) != 0)
         return -EINVAL;
-    if ((router->flags & ZMQG_ROUTER_PREPEND) && args->n_streams > 0 && (!router->src_id_off || !router->src_id_len))
+    const bool prepend = router->flags & ZMQG_ROUTER_PREPEND, route = router->flags & ZMQG_ROUTER_ROUTE;
+    if (prepend && args->n_streams > 0 && (!router->src_id_off || !router->src_id_len))
         return -EINVAL;
-    if ((router->flags & ZMQG_ROUTER_ROUTE) &&
+    if (route &&
         (check_n(router->n_ids) || (router->n_ids > 0 && (!router->id_off || !router->id_len || !router->id_dst)) ||
          (router->id_bytes_len > 0 && !router->id_bytes)))
         return -EINVAL;
-    return forward_multi_impl(ctx, args, nullptr, router->flags ? router : nullptr, nullptr, stream);
+    if (!router->flags)
+        return zmqg_forward_zmtp_multi(ctx, args, stream);
+    // ROUTE: one route slot a stream; PREPEND alone: an id slot in front of every element
+    const FwdTableIn in = {args, route, true, prepend && !route ? 2u : 1u, nullptr, 0};
+    FwdCall c;
+    int rc;
+    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_router(ctx, c, *router)))
+        return rc;
+    return forward_finish(ctx, c);
 }
 
 // The load balancer's launch-free checks: the struct, and stream_group, the one
@@ -3706,7 +3418,13 @@ int zmqg_forward_zmtp_lb_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, con
     for (uint64_t s = 0; s < args->n_streams; ++s)
         if (lb->stream_group[s] != ZMQG_LB_NO_GROUP && lb->stream_group[s] >= lb->n_groups)
             return -EINVAL;
-    return forward_multi_impl(ctx, args, nullptr, nullptr, lb, stream);
+    // one route slot a stream; PREPEND: an id slot in front of every element
+    const FwdTableIn in = {args, true, true, lb->flags & ZMQG_LB_PREPEND ? 2u : 1u, lb->stream_group, lb->n_groups};
+    FwdCall c;
+    int rc;
+    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_lb(ctx, c, *lb)))
+        return rc;
+    return forward_finish(ctx, c);
 }
 
 // The launch-free checks, the two host arrays through the pinned staging, then
@@ -3756,7 +3474,7 @@ int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *st
     if ((rc = order_after_last(ctx, st)))
         return rc;
     const SubsStore store{D, a.cap, a.slot_bytes, a.cnt, a.slot_len, a.bytes};
-    const uint64_t EC = C * a.cap, E = EC + S * MF, per = kSubsThreads / 64u; // (E < 2^32)
+    const uint64_t EC = C * a.cap, E = EC + S * MF; // (E < 2^32)
     const uint32_t *d_sdst = nullptr, *d_cdst = nullptr;
     if (S + C > 0) {
         if ((rc = sinst_room(ctx, 4 * (size_t) (S + C))))
@@ -3771,15 +3489,10 @@ int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *st
         d_sdst = z.u_tab;
         d_cdst = d_sdst + S;
     }
-    if (E > z.u_cap) {
-        const uint64_t cap = grown_cap(z.u_cap, 1024, E);
-        z.u_cap = 0;
-        ZRESERVE(ctx, z.u_h0, cap, st);
-        ZRESERVE(ctx, z.u_delta, cap, st);
-        z.u_cap = cap;
-    }
+    if ((rc = reserve_group(ctx, st, "u_h0, u_delta", z.u_cap, 1024, E, z.u_h0, z.u_delta)))
+        return rc;
     if (S * MF > 0) {
-        hipLaunchKernelGGL(k_subs_classify, dim3((unsigned) ((S + per - 1) / per)), dim3(kSubsThreads), 0, st,
+        hipLaunchKernelGGL(k_subs_classify, dim3(wave_grid(S, kSubsThreads)), dim3(kSubsThreads), 0, st,
                            (uint32_t) S, MF, a.results, a.frame_len, a.plain_off, a.flags_out, a.status_out, a.plain,
                            a.sub_status, a.topic_off, a.topic_len, a.note_flags, a.note_stream, z.u_delta.p + EC);
         ZCHECK(ctx, hipGetLastError());
@@ -3792,14 +3505,14 @@ int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *st
         ZCHECK(ctx, hipGetLastError());
     }
     if (S + C > 0) {
-        hipLaunchKernelGGL(k_subs_apply, dim3((unsigned) ((S + C + per - 1) / per)), dim3(kSubsThreads), 0, st,
+        hipLaunchKernelGGL(k_subs_apply, dim3(wave_grid(S + C, kSubsThreads)), dim3(kSubsThreads), 0, st,
                            (uint32_t) S, MF, (uint32_t) C, EC, store, d_sdst, d_cdst, (const uint8_t *) a.note_flags,
                            (const uint64_t *) a.topic_off, (const uint32_t *) a.topic_len, a.plain, a.sub_status,
                            z.u_delta.p, (SubsResult *) a.results_out, a.clear_cnt, a.clear_len);
         ZCHECK(ctx, hipGetLastError());
     }
     if (E > 0) {
-        hipLaunchKernelGGL(k_subs_resolve, dim3((unsigned) ((E + per - 1) / per)), dim3(kSubsThreads), 0, st, E, EC, MF,
+        hipLaunchKernelGGL(k_subs_resolve, dim3(wave_grid(E, kSubsThreads)), dim3(kSubsThreads), 0, st, E, EC, MF,
                            a.flags, store, d_cdst, (const uint32_t *) a.clear_cnt, (const uint8_t *) a.note_flags,
                            (const uint64_t *) a.topic_off, (const uint32_t *) a.topic_len, a.plain,
                            (const int32_t *) a.sub_status, (const int8_t *) z.u_delta.p, (const uint32_t *) z.u_h0.p,
@@ -3861,12 +3574,10 @@ int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stre
     }
     // 3. the decode over every slot, as in zmqg_decode_zmtp_multi; masked
     // bodies are read where the unmask put them
-    zmqg_batch_opts o{};
-    o.size = sizeof o;
-    if (max_msg_size >= 0 && (uint64_t) max_msg_size <= kMaxFrameStream)
-        o.max_len = max_msg_size > 0 ? (uint64_t) max_msg_size : 1u;
+    zmqg_batch_opts o;
     return decode_batch_impl(ctx, slots, z.sid_fill, frame_in_off, frame_len, must_mask ? out : in, out_off, out,
-                             flags_out, status_out, o.max_len ? &o : nullptr, z.fflags, nullptr, nullptr, stream);
+                             flags_out, status_out, decode_len_bound(max_msg_size, &o), z.fflags, nullptr, nullptr,
+                             stream);
 }
 
 int zmqg_decode_zmtp(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint64_t in_bytes, int64_t max_msg_size,
