@@ -250,7 +250,11 @@ int zmqg_decode_batch(zmqg_ctx *ctx, uint64_t n, const uint32_t *sid, const uint
  *                    kernel (stream <= 4.5 KiB: decode wire_len <= 4608, encode
  *                    len <= 4565) lets the call skip the large-frame kernels
  *                    (two fewer launches).  A frame above the bound fails with
- *                    ZMQG_ERR_BOUND.
+ *                    ZMQG_ERR_BOUND.  Under ZMQG_OPT_NONCE_AUTO such a frame
+ *                    of a known session still takes its nonce (the session's
+ *                    counter counts every frame of the batch that names it,
+ *                    with one session and with several), so the nonces on
+ *                    the wire have a gap there.
  *   status_out       encode only: n entries (device-accessible), 0 or
  *                    ZMQG_ERR_SESSION / ZMQG_ERR_BOUND per frame.
  *   session_max_out  decode only: max_sessions entries (device-accessible):

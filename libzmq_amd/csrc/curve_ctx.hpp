@@ -116,7 +116,7 @@ struct zmqg_ctx {
     int device = 0;
     int cus = 256; // compute units of the device (one persistent body workgroup each)
     uint32_t max_sessions = 0;
-    int sort_bits = 0;
+    int sort_bits = 0; // ceil(log2(max_sessions)); > 0: several sessions (the replay tables or the sort fallback)
     DevSession *sessions = nullptr;
     unsigned long long *peer = nullptr; // [max_sessions]
     unsigned long long *send = nullptr; // [max_sessions] send nonces (_cn_nonce) for ZMQG_OPT_NONCE_AUTO
@@ -302,7 +302,7 @@ int ensure_workspace(zmqg_ctx *ctx, uint64_t n, hipStream_t st)
         size_t need = 0, b = 0;
         ZCHECK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const uint32_t *) nullptr, w.keys_s.p,
                                                         (const uint32_t *) nullptr, w.perm.p, (int) n, 0,
-                                                        ctx->sort_bits));
+                                                        kSortKeyBits));
         ZCHECK(ctx, hipcub::DeviceScan::ExclusiveScanByKey(nullptr, b, w.keys_s.p, w.v_s.p, w.excl_s.p, hipcub::Max(),
                                                             0ull, (int) n));
         need = b > need ? b : need;

@@ -77,6 +77,11 @@ constexpr int kHeadThreads = 256;
 constexpr uint32_t kMaxFrameStream = 64 * 72; // frames up to 4.5 KiB of stream: frame kernel
 constexpr int kFixupThreads = 256;
 constexpr uint32_t kReplayMaxSessions = 8192; // the replay tables' limit; more sessions take the sort fallback
+// The sort fallback orders the caller's sid array on all of its bits: a sid >=
+// max_sessions (ZMQG_ERR_SESSION, the frame is not processed) whose low
+// ceil(log2(max_sessions)) bits are a session's id would otherwise sort into
+// that session's run and cut its scan segment in two.
+constexpr int kSortKeyBits = 32;
 
 // Per-frame records written by the head kernel and read by the body kernel,
 // grouped by when a body lane needs them so each group is one batch of
@@ -2065,7 +2070,7 @@ int replay_multi(zmqg_ctx *ctx, uint32_t nn, const uint32_t *sid, hipStream_t st
     const dim3 hgrid((nn + kHeadThreads - 1) / kHeadThreads);
     size_t tb = w.temp.count;
     ZCHECK(ctx, hipcub::DeviceRadixSort::SortPairs(w.temp.p, tb, sid, w.keys_s.p, w.iota.p, w.perm.p, (int) nn, 0,
-                                                    ctx->sort_bits, st));
+                                                    kSortKeyBits, st));
     hipLaunchKernelGGL(k_gather_u64, hgrid, dim3(kHeadThreads), 0, st, nn, w.perm, w.v, w.v_s);
     ZCHECK(ctx, hipGetLastError());
     tb = w.temp.count;

@@ -103,6 +103,11 @@ _lib.zmqg_decode_zmtp_multi.argtypes = [_P, _U64] + [_P] * 4 + [ctypes.c_int64, 
 _lib.zmqg_encode_zmtp_multi.argtypes = [_P, _U64, _P, _U64] + [_P] * 7 + [_U64] + [_P] * 4
 ZMTP_MULTI_TILE = 16384  # kZmtpMultiTile: bytes of a stream zmqg_decode_zmtp_multi's kernel holds in LDS at a time
 ZMTP_SCAN_TILE = 16384  # kZmtpWgBytes: bytes of a stream one workgroup of zmqg_decode_zmtp's candidate scan lists
+REPLAY_TILE_MIN = 256  # replay_tile_frames' first T: the fewest frames of a tile of the tables k_replay_*, k_nonce_*
+REPLAY_ROW_BLOCK = 64  # kReplayRB: table rows (tiles) per block of the tables' column passes
+REPLAY_MAX_TILES = 4096  # kReplayMaxTiles: above this many tiles the tile doubles
+REPLAY_MAX_SESSIONS = 8192  # kReplayMaxSessions: the tables' limit; more sessions take the sort fallback (decode only)
+ZSEND_MAX_TILES = 4096  # kZsendMaxTiles: the same bound for zmqg_encode_zmtp_multi's tables (zsend_tile_frames)
 
 
 class ForwardResult(ctypes.Structure):  # zmqg_forward_result

@@ -433,7 +433,7 @@ def test_multi_session_replay_vs_oracle(torch_cuda, C, n_sessions, n):
     keys = _keys(rng, n_sessions)
     sizes = rng.integers(0, 200, n)
     sid = rng.integers(0, n_sessions, n).astype(np.uint32)
-    sid[100:164] = sid[100]  # one session filling a whole wave
+    sid[100:164] = sid[100]  # 64 frames in a row of one session: parts of two 64-frame steps of k_replay_frames
     nonce = rng.integers(3, 60, n).astype(np.uint64) + np.arange(n, dtype=np.uint64) // 3
     flags = rng.choice([0, 1, 3], n).astype(np.uint8)
     wire, woff, wl, _ = _wire_batch(torch, C, rng, keys, sizes, sid, nonce, flags)
