@@ -59,6 +59,10 @@
  *   lb_t::sendpipe (dealer_t::sendpipe, push_t::xsend)
  *     src/lb.cpp:56-131, src/dealer.cpp:110-113,
  *     src/push.cpp:45-48                             zmqg_forward_zmtp_lb_multi
+ *   ws_engine_t on either side of zmq_proxy's forward
+ *     src/proxy.cpp:90-138,
+ *     src/ws_decoder.cpp:39-249,
+ *     src/ws_encoder.cpp:26-126                      zmqg_forward_framed_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -717,7 +721,7 @@ int zmqg_encode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
  * one copy of the HOST arrays, two for the plan (one wave per source stream;
  * one lane per pair), then zmqg_encode_zmtp_multi's with device nonces (nine
  * before the encode's own), whatever the sizes are.  WebSocket framing on
- * either side is not offered on this call; routing by XPUB topics is
+ * either side is zmqg_forward_framed_multi; routing by XPUB topics is
  * zmqg_forward_zmtp_sub_multi, routing by ROUTER identities
  * zmqg_forward_zmtp_router_multi, DEALER's and PUSH's round-robin choice per
  * message (lb_t) zmqg_forward_zmtp_lb_multi: route_dst is per stream and per
@@ -838,7 +842,8 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
  * SUBSCRIBE / CANCEL commands (they stay held commands for the host;
  * zmqg_subs_update_multi, a call of its own, keeps such a table);
  * ZMQ_XPUB_MANUAL, ZMQ_XPUB_NODROP and high-water marks, the welcome message;
- * the XSUB upstream direction; WebSocket framing. */
+ * the XSUB upstream direction; WebSocket framing here (it is
+ * zmqg_forward_framed_multi with ZMQG_FWD_SUB). */
 #define ZMQG_SUBS_INVERT 1u            /* options.invert_matching: dist_t::reverse_match, src/dist.cpp:64-78 */
 typedef struct zmqg_forward_subs {
     uint32_t size, flags;              /* sizeof(zmqg_forward_subs); 0 or ZMQG_SUBS_INVERT */
@@ -1120,7 +1125,8 @@ int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *st
  * Not offered: ZMQ_ROUTER_MANDATORY and its errors, ZMQ_ROUTER_HANDOVER,
  * ZMQ_ROUTER_RAW; maintaining the id table on the device; DEALER's round-robin
  * choice (lb_t), which is zmqg_forward_zmtp_lb_multi (with its own PREPEND for
- * a ROUTER frontend); high-water marks; WebSocket framing; combining with the
+ * a ROUTER frontend); high-water marks; WebSocket framing here (it is
+ * zmqg_forward_framed_multi with ZMQG_FWD_ROUTER); combining with the
  * subscription table. */
 #define ZMQG_ROUTER_PREPEND 1u   /* receive side is a ROUTER: router_t::xrecv */
 #define ZMQG_ROUTER_ROUTE   2u   /* send side is a ROUTER: router_t::xsend */
@@ -1236,8 +1242,9 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
  * Not offered: high-water marks and lb_t's deactivation of a full pipe
  * (src/lb.cpp:103-107): the host keeps a pipe that is not writable out of
  * lb_dst; the exact turn after a membership change (the host edits the range
- * without reading the cursor, the device clamps it); WebSocket framing;
- * combining with the subscription or the id table. */
+ * without reading the cursor, the device clamps it); WebSocket framing here
+ * (it is zmqg_forward_framed_multi with ZMQG_FWD_LB); combining with the
+ * subscription or the id table. */
 #define ZMQG_LB_PREPEND  1u           /* receive side is a ROUTER: as ZMQG_ROUTER_PREPEND */
 #define ZMQG_LB_NO_GROUP 0xffffffffu  /* stream_group[s]: this stream's messages are not distributed */
 #define ZMQG_LB_NONE     0xffffffffu  /* dest_out: slot not forwarded (held, command, past seq, unused id slot) */
@@ -1356,6 +1363,91 @@ int zmqg_encode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stre
                          const uint64_t *in_off, const uint32_t *len, const uint8_t *in, const uint32_t *mask,
                          uint8_t *out, uint64_t out_bytes, uint64_t *frame_off, int32_t *status_out,
                          zmqg_zmtp_send_result *results, void *stream);
+
+/* zmqg_forward_framed_multi: the four forward calls with a framing chosen for
+ * each side -- a proxy whose one side is ws_engine_t (src/ws_engine.cpp) and
+ * whose other side is the ZMTP engine, or WebSocket on both: zmq_proxy's
+ * forward (src/proxy.cpp:90-138) between ws_decoder_t (src/ws_decoder.cpp:
+ * 39-249) and ws_encoder_t (src/ws_encoder.cpp:26-126).  The framing is
+ * orthogonal to the routing rule: statuses, MORE / COMMAND bits, frame counts
+ * and the payloads in `plain` come out of either decoder in the same slot
+ * layout, and the plan reads nothing else.
+ *
+ * Relation to the existing calls.  `args` is zmqg_forward_zmtp_multi's struct.
+ * framing->mode names the rule and framing->plan its struct:
+ *   ZMQG_FWD_STATIC  zmqg_forward_zmtp_multi, plan == NULL
+ *   ZMQG_FWD_SUB     zmqg_forward_zmtp_sub_multi, plan a zmqg_forward_subs
+ *   ZMQG_FWD_ROUTER  zmqg_forward_zmtp_router_multi, plan a zmqg_forward_router
+ *                    (flags == 0 is the static rule, as there)
+ *   ZMQG_FWD_LB      zmqg_forward_zmtp_lb_multi, plan a zmqg_forward_lb
+ * The contract is the one stated for the mode's own call, with two
+ * substitutions and nothing else changed: zmqg_decode_ws_multi replaces
+ * zmqg_decode_zmtp_multi on the receive side when recv is not ZMTP, and
+ * zmqg_encode_ws_multi replaces zmqg_encode_zmtp_multi on the send side when
+ * send is not ZMTP.  The sequence Q(s) with F, E and fwd[s], the carry, the
+ * pair space and N of the mode, live pairs, match_out and dest_out, lb_cur, the
+ * nonces in pair order, fit, ENOBUFS and the prefix property are the mode's.
+ * With recv == send == ZMQG_FRAMING_ZMTP the call is the mode's own call, byte
+ * for byte and nonce for nonce.
+ *
+ * Receive side, recv = ZMQG_FRAMING_WS or _WS_MASKED.  Every output is what
+ * zmqg_decode_ws_multi writes with must_mask = (recv == ZMQG_FRAMING_WS_MASKED):
+ * slots, statuses and flags with the frame's MORE / COMMAND bits from the
+ * WebSocket flags byte, the payloads at the body's offset in plain, plain == in
+ * with masked bodies unmasked and decoded in place, the peer nonces, EPROTO and
+ * EMSGSIZE, a stream that ends at a control frame.  The results go to
+ * framing->ws_results (n_streams entries); args->results is neither read nor
+ * written and may be NULL.  A close / ping / pong frame ends its stream's parse
+ * exactly as in zmqg_decode_ws_multi: the frames returned before it are in Q(s)
+ * and are forwarded by the usual rule; the host answers it from ctl_opcode /
+ * ctl_off / ctl_len and submits the rest of the buffer from `consumed` in its
+ * next call; a message that is open reaches across the control frame through
+ * the carry, like any other held part.  max_frames == 0 zero-fills ws_results.
+ *
+ * Send side, send = ZMQG_FRAMING_WS or _WS_MASKED.  Exactly
+ * zmqg_encode_ws_multi over the N pairs; a pair's liveness, flags, offset and
+ * length come from the plan as in the mode's call.  mask is NULL for
+ * ZMQG_FRAMING_WS and framing->mask for _WS_MASKED: N device-accessible
+ * entries indexed by pair index p, of which only those of live, fitting pairs
+ * are read.  The host knows N before the call (from carry_idx, route_idx and
+ * the mode) and fills N words from its random source, as for
+ * zmqg_encode_ws_multi.  dst_results[t].out_off / out_bytes are the peer's
+ * zmqg_decode_ws_multi stream_off / stream_len.
+ *
+ * Members a chosen framing does not use (ws_results, mask, args->results) are
+ * neither read nor written.
+ * Returns -EINVAL, with nothing queued, for a null framing, size !=
+ * sizeof(zmqg_forward_framing), a non-zero reserved or reserved2, recv, send or
+ * mode out of range, a non-NULL plan with ZMQG_FWD_STATIC and a NULL plan
+ * otherwise, the plan struct's own size / flag cases as its call makes them,
+ * recv != ZMTP with n_streams > 0 and a null ws_results, recv == ZMTP with a
+ * null args->results, send == ZMQG_FRAMING_WS_MASKED with N > 0 and a null
+ * mask, and every case of the mode's own call.
+ * Launches: the sum of the parts.  The mode's own, and: a masked receive side
+ * takes zmqg_decode_ws_multi's two launches more than a batch decode where
+ * zmqg_decode_zmtp_multi takes one; an unmasked receive side one, and two
+ * when a control payload has to be copied to a plain that is not in; a masked
+ * send side the one XOR launch behind the encode.
+ * Out of scope: a framing per stream or per destination within one call (an
+ * XPUB bound to tcp:// and ws:// at once makes two calls); answering pings on
+ * the device; ZMQG_OPT_* on this call. */
+#define ZMQG_FRAMING_ZMTP      0u
+#define ZMQG_FRAMING_WS        1u   /* WebSocket, unmasked: a server's send side, a client's receive side */
+#define ZMQG_FRAMING_WS_MASKED 2u   /* WebSocket, masked: a server's receive side (must_mask), a client's send side */
+#define ZMQG_FWD_STATIC 0u          /* zmqg_forward_zmtp_multi's rule; plan == NULL */
+#define ZMQG_FWD_SUB    1u          /* plan: const zmqg_forward_subs * */
+#define ZMQG_FWD_ROUTER 2u          /* plan: const zmqg_forward_router * */
+#define ZMQG_FWD_LB     3u          /* plan: const zmqg_forward_lb * */
+typedef struct zmqg_forward_framing {   /* 48 bytes */
+    uint32_t size, reserved;        /* sizeof(zmqg_forward_framing), 0 */
+    uint32_t recv, send;            /* ZMQG_FRAMING_* of the receive buffers / of the send runs */
+    uint32_t mode, reserved2;       /* ZMQG_FWD_*, 0 */
+    const void *plan;               /* the mode's struct */
+    zmqg_ws_result *ws_results;     /* recv != ZMTP: n_streams entries, device-accessible */
+    const uint32_t *mask;           /* send == WS_MASKED: N entries, device-accessible */
+} zmqg_forward_framing;
+int zmqg_forward_framed_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
+                              const zmqg_forward_framing *framing, void *stream);
 
 /* Handshake key derivation in batches, one
  * 32-byte item per thread, items packed back to back:

@@ -33,7 +33,10 @@
 
 namespace zmqg {
 
-__global__ __launch_bounds__(kFwdThreads) void k_fwd_scan(FwdSrc src, const zmqg_zmtp_result *__restrict__ results,
+// Result: the receive side's per-stream result, zmqg_zmtp_result or
+// zmqg_ws_result; `frames` is all that is read of it.
+template <class Result>
+__global__ __launch_bounds__(kFwdThreads) void k_fwd_scan(FwdSrc src, const Result *__restrict__ results,
                                                          zmqg_forward_result *__restrict__ fwd)
 {
     const uint32_t lane = threadIdx.x & 63u, s = blockIdx.x * (kFwdThreads / 64u) + (threadIdx.x >> 6);

@@ -1,4 +1,4 @@
-// curve_fwd_host.hpp -- the host path of the four forward calls: forward_begin,
+// curve_fwd_host.hpp -- the host path of the forward calls: forward_begin,
 // the entry's own fwd_plan_*, forward_finish ("Forwarding").  Part of
 // zmqg_curve.hip, included there after the receive and send sides it queues.
 #pragma once
@@ -6,10 +6,23 @@
 
 static_assert(kFwdNoStream == kZsendNoSession, "curve_fwd_common.hpp restates the send side's value");
 
+// The framing of the two sides (ZMQG_FRAMING_*): what decodes the receive
+// buffers, what encodes the send runs.  The plan between them reads slots and
+// fwd[s] only, which either decoder fills alike.  The four zmqg_forward_zmtp_*
+// entries pass kFwdFramingZmtp; zmqg_forward_framed_multi the caller's choice.
+struct FwdFraming {
+    uint32_t recv, send;
+    zmqg_ws_result *ws_results; // recv != ZMTP: takes the place of args->results
+    const uint32_t *mask;       // send == WS_MASKED: one key per pair
+    bool ws_recv() const { return recv != ZMQG_FRAMING_ZMTP; }
+};
+static const FwdFraming kFwdFramingZmtp = {ZMQG_FRAMING_ZMTP, ZMQG_FRAMING_ZMTP, nullptr, nullptr};
+
 struct FwdCall {
     std::unique_lock<std::mutex> lk; // ctx->mu, from forward_begin to the end of the call
     const zmqg_forward_zmtp *a;
     hipStream_t st;
+    FwdFraming fr;
     FwdTableDims t; // t.N pairs, t.EN elements of the routed streams
     FwdTab tab;
     FwdSrc src;
@@ -17,15 +30,15 @@ struct FwdCall {
     bool empty() const { return a->n_streams == 0; } // nothing to queue
 };
 
-static int forward_begin(zmqg_ctx *ctx, const FwdTableIn &in, void *stream, FwdCall &c)
+static int forward_begin(zmqg_ctx *ctx, const FwdTableIn &in, const FwdFraming &fr, void *stream, FwdCall &c)
 {
     const zmqg_forward_zmtp *args = in.a;
     if (!ctx || !args || args->size != sizeof *args || args->reserved != 0)
         return -EINVAL;
     const zmqg_forward_zmtp &a = *args;
     const uint64_t S = a.n_streams, MF = a.max_frames;
-    // the two underlying calls' own cases
-    if (!a.results || check_n(S) || check_n(MF) || check_n(S * MF))
+    // the two underlying calls' own cases (the results array is the receive framing's)
+    if ((fr.ws_recv() ? S > 0 && !fr.ws_results : !a.results) || check_n(S) || check_n(MF) || check_n(S * MF))
         return -EINVAL;
     if (a.n_dst > kZsendMaxStreams || ctx->max_sessions > kReplayMaxSessions)
         return -EINVAL;
@@ -33,6 +46,7 @@ static int forward_begin(zmqg_ctx *ctx, const FwdTableIn &in, void *stream, FwdC
     ZCHECK(ctx, hipSetDevice(ctx->device));
     c.a = args;
     c.st = st;
+    c.fr = fr;
     if (S == 0)
         return 0;
     if (MF > 0 && (!a.stream_sid || !a.stream_off || !a.stream_len || !a.in || !a.frame_in_off || !a.frame_len ||
@@ -47,7 +61,7 @@ static int forward_begin(zmqg_ctx *ctx, const FwdTableIn &in, void *stream, FwdC
     const uint64_t N = t.N;
     if (a.carry_idx && a.carry_idx[S] > 0 && (!a.carry_off || !a.carry_len || !a.carry_flags))
         return -EINVAL;
-    if (N > 0 && (!a.plain || !a.out))
+    if (N > 0 && (!a.plain || !a.out || (fr.send == ZMQG_FRAMING_WS_MASKED && !fr.mask)))
         return -EINVAL;
     // (the send side's own case: frames and no streams; routes cannot name none)
     if (in.one_route && N > 0 && a.n_dst == 0)
@@ -73,25 +87,49 @@ static int forward_begin(zmqg_ctx *ctx, const FwdTableIn &in, void *stream, FwdC
     return 0;
 }
 
-// The receive side, then what each stream forwards
+// The receive side in its framing, then what each stream forwards
 static int forward_receive(zmqg_ctx *ctx, const FwdCall &c)
 {
     const zmqg_forward_zmtp &a = *c.a;
     const uint64_t S = a.n_streams, MF = a.max_frames;
+    const dim3 grid(wave_grid(S, kFwdThreads)), block(kFwdThreads);
     int rc;
-    if (MF == 0)
-        ZCHECK(ctx, hipMemsetAsync(a.results, 0, S * sizeof *a.results, c.st));
-    else if ((rc = decode_zmtp_multi_locked(ctx, S, a.stream_sid, a.stream_off, a.stream_len, a.in, a.max_msg_size, MF,
-                                            a.frame_in_off, a.frame_len, a.plain_off, a.plain, a.flags_out,
-                                            a.status_out, a.results, c.st)))
-        return rc;
-    hipLaunchKernelGGL(k_fwd_scan, dim3(wave_grid(S, kFwdThreads)), dim3(kFwdThreads), 0, c.st, c.src, a.results,
-                       a.fwd);
+    if (c.fr.ws_recv()) {
+        zmqg_ws_result *res = c.fr.ws_results;
+        if (MF == 0)
+            ZCHECK(ctx, hipMemsetAsync(res, 0, S * sizeof *res, c.st));
+        else if ((rc = decode_ws_multi_locked(ctx, S, a.stream_sid, a.stream_off, a.stream_len, a.in,
+                                              c.fr.recv == ZMQG_FRAMING_WS_MASKED, a.max_msg_size, MF, a.frame_in_off,
+                                              a.frame_len, a.plain_off, a.plain, a.flags_out, a.status_out, res,
+                                              c.st)))
+            return rc;
+        hipLaunchKernelGGL(k_fwd_scan<zmqg_ws_result>, grid, block, 0, c.st, c.src, (const zmqg_ws_result *) res,
+                           a.fwd);
+    } else {
+        if (MF == 0)
+            ZCHECK(ctx, hipMemsetAsync(a.results, 0, S * sizeof *a.results, c.st));
+        else if ((rc = decode_zmtp_multi_locked(ctx, S, a.stream_sid, a.stream_off, a.stream_len, a.in,
+                                                a.max_msg_size, MF, a.frame_in_off, a.frame_len, a.plain_off, a.plain,
+                                                a.flags_out, a.status_out, a.results, c.st)))
+            return rc;
+        hipLaunchKernelGGL(k_fwd_scan<zmqg_zmtp_result>, grid, block, 0, c.st, c.src,
+                           (const zmqg_zmtp_result *) a.results, a.fwd);
+    }
     ZCHECK(ctx, hipGetLastError());
     return 0;
 }
 
-// The send side: the pairs are its frames, the destinations its streams
+// The send side in its framing: the pairs are its frames, the destinations its
+// streams, a masked pair's key mask[p]
+extern "C++" template <ZsendFraming FR>
+static int forward_send(zmqg_ctx *ctx, const FwdCall &c, const uint32_t *mask)
+{
+    const zmqg_forward_zmtp &a = *c.a;
+    return encode_multi_locked<FR>(ctx, a.n_dst, a.dst_sid, c.t.N, c.out.p_stream, nullptr, c.out.p_flags, c.out.p_off,
+                                   c.out.p_len, a.plain, mask, a.out, a.out_bytes, a.pair_off, a.pair_status,
+                                   a.dst_results, c.st);
+}
+
 static int forward_finish(zmqg_ctx *ctx, const FwdCall &c)
 {
     const zmqg_forward_zmtp &a = *c.a;
@@ -99,9 +137,11 @@ static int forward_finish(zmqg_ctx *ctx, const FwdCall &c)
         ZCHECK(ctx, hipMemsetAsync(a.pair_off, 0, sizeof(uint64_t), c.st));
         return 0;
     }
-    return encode_multi_locked<kZsendZmtp>(ctx, a.n_dst, a.dst_sid, c.t.N, c.out.p_stream, nullptr, c.out.p_flags,
-                                           c.out.p_off, c.out.p_len, a.plain, nullptr, a.out, a.out_bytes, a.pair_off,
-                                           a.pair_status, a.dst_results, c.st);
+    if (c.fr.send == ZMQG_FRAMING_WS_MASKED)
+        return forward_send<kZsendWsMasked>(ctx, c, c.fr.mask);
+    if (c.fr.send == ZMQG_FRAMING_WS)
+        return forward_send<kZsendWs>(ctx, c, nullptr);
+    return forward_send<kZsendZmtp>(ctx, c, nullptr);
 }
 
 // zmqg_forward_zmtp_multi: the pairs (one lane per pair)

@@ -3348,22 +3348,31 @@ int zmqg_decode_zmtp_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *st
                                     frame_in_off, frame_len, out_off, out, flags_out, status_out, results, stream);
 }
 
+// (zmqg_decode_ws_multi behind its argument checks, defined with that call below)
+static int decode_ws_multi_locked(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid,
+                                  const uint64_t *stream_off, const uint32_t *stream_len, const uint8_t *in,
+                                  bool must_mask, int64_t max_msg_size, uint64_t max_frames, uint64_t *frame_in_off,
+                                  uint32_t *frame_len, uint64_t *out_off, uint8_t *out, uint8_t *flags_out,
+                                  int32_t *status_out, zmqg_ws_result *results, void *stream);
+
 #include "curve_fwd_host.hpp" // forward_begin, fwd_plan_*, forward_finish
 
-int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
+// The four routing rules, each with the framing of its two sides: the entry of
+// its own name passes ZMTP on both, zmqg_forward_framed_multi the caller's.
+static int forward_static(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const FwdFraming &fr, void *stream)
 {
     const FwdTableIn in = {args, false, false, 1u, nullptr, 0};
     FwdCall c;
     int rc;
-    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_static(ctx, c)))
+    if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_static(ctx, c)))
         return rc;
     return forward_finish(ctx, c);
 }
 
 // The table's launch-free checks; what the host cannot see (sub_idx's entries,
 // the subscriptions' extents) the match kernel bounds itself.
-int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
-                                void *stream)
+static int forward_sub(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
+                       const FwdFraming &fr, void *stream)
 {
     if (!ctx || !args || !subs || subs->size != sizeof *subs || (subs->flags & ~ZMQG_SUBS_INVERT) != 0)
         return -EINVAL;
@@ -3373,15 +3382,15 @@ int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, co
     const FwdTableIn in = {args, false, true, 1u, nullptr, 0};
     FwdCall c;
     int rc;
-    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_sub(ctx, c, *subs)))
+    if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_sub(ctx, c, *subs)))
         return rc;
     return forward_finish(ctx, c);
 }
 
 // The router struct's launch-free checks; the id table's contents the lookup
 // bounds itself (curve_fwd_route.hpp).  flags == 0 is zmqg_forward_zmtp_multi.
-int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_router *router,
-                                   void *stream)
+static int forward_router(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_router *router,
+                          const FwdFraming &fr, void *stream)
 {
     if (!ctx || !args || !router || router->size != sizeof *router ||
         (router->flags & ~(ZMQG_ROUTER_PREPEND | ZMQG_ROUTER_ROUTE)) != 0)
@@ -3394,12 +3403,12 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
          (router->id_bytes_len > 0 && !router->id_bytes)))
         return -EINVAL;
     if (!router->flags)
-        return zmqg_forward_zmtp_multi(ctx, args, stream);
+        return forward_static(ctx, args, fr, stream);
     // ROUTE: one route slot a stream; PREPEND alone: an id slot in front of every element
     const FwdTableIn in = {args, route, true, prepend && !route ? 2u : 1u, nullptr, 0};
     FwdCall c;
     int rc;
-    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_router(ctx, c, *router)))
+    if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_router(ctx, c, *router)))
         return rc;
     return forward_finish(ctx, c);
 }
@@ -3407,7 +3416,8 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
 // The load balancer's launch-free checks: the struct, and stream_group, the one
 // array of it the host can see.  grp_idx, lb_dst and lb_cur live on the device;
 // the kernels bound every read of them (curve_fwd_lb.hpp).
-int zmqg_forward_zmtp_lb_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_lb *lb, void *stream)
+static int forward_lb(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_lb *lb, const FwdFraming &fr,
+                      void *stream)
 {
     if (!ctx || !args || !lb || lb->size != sizeof *lb || (lb->flags & ~ZMQG_LB_PREPEND) != 0)
         return -EINVAL;
@@ -3427,9 +3437,59 @@ int zmqg_forward_zmtp_lb_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, con
     const FwdTableIn in = {args, true, true, lb->flags & ZMQG_LB_PREPEND ? 2u : 1u, lb->stream_group, lb->n_groups};
     FwdCall c;
     int rc;
-    if ((rc = forward_begin(ctx, in, stream, c)) || c.empty() || (rc = fwd_plan_lb(ctx, c, *lb)))
+    if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_lb(ctx, c, *lb)))
         return rc;
     return forward_finish(ctx, c);
+}
+
+int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *stream)
+{
+    return forward_static(ctx, args, kFwdFramingZmtp, stream);
+}
+
+int zmqg_forward_zmtp_sub_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
+                                void *stream)
+{
+    return forward_sub(ctx, args, subs, kFwdFramingZmtp, stream);
+}
+
+int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_router *router,
+                                   void *stream)
+{
+    return forward_router(ctx, args, router, kFwdFramingZmtp, stream);
+}
+
+int zmqg_forward_zmtp_lb_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_lb *lb, void *stream)
+{
+    return forward_lb(ctx, args, lb, kFwdFramingZmtp, stream);
+}
+
+// The framing struct's launch-free checks, then the mode's rule with its own;
+// what depends on the sizes (ws_results with streams, mask with pairs) is
+// forward_begin's.
+int zmqg_forward_framed_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_framing *framing,
+                              void *stream)
+{
+    if (!ctx || !args || !framing || framing->size != sizeof *framing || framing->reserved != 0 ||
+        framing->reserved2 != 0)
+        return -EINVAL;
+    if (framing->recv > ZMQG_FRAMING_WS_MASKED || framing->send > ZMQG_FRAMING_WS_MASKED ||
+        framing->mode > ZMQG_FWD_LB || (framing->mode == ZMQG_FWD_STATIC) != !framing->plan)
+        return -EINVAL;
+    // (members the framing does not use are not passed on)
+    const FwdFraming fr = {framing->recv, framing->send,
+                           framing->recv != ZMQG_FRAMING_ZMTP ? framing->ws_results : nullptr,
+                           framing->send == ZMQG_FRAMING_WS_MASKED ? framing->mask : nullptr};
+    switch (framing->mode) {
+    case ZMQG_FWD_SUB:
+        return forward_sub(ctx, args, (const zmqg_forward_subs *) framing->plan, fr, stream);
+    case ZMQG_FWD_ROUTER:
+        return forward_router(ctx, args, (const zmqg_forward_router *) framing->plan, fr, stream);
+    case ZMQG_FWD_LB:
+        return forward_lb(ctx, args, (const zmqg_forward_lb *) framing->plan, fr, stream);
+    default:
+        return forward_static(ctx, args, fr, stream);
+    }
 }
 
 // The launch-free checks, the two host arrays through the pinned staging, then
@@ -3530,25 +3590,15 @@ int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *st
     return 0;
 }
 
-int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
-                         const uint32_t *stream_len, const uint8_t *in, int must_mask, int64_t max_msg_size,
-                         uint64_t max_frames, uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off,
-                         uint8_t *out, uint8_t *flags_out, int32_t *status_out, zmqg_ws_result *results, void *stream)
+// zmqg_decode_ws_multi behind its argument checks, n_streams and max_frames > 0,
+// under ctx->mu (also the receive side of zmqg_forward_framed_multi).
+static int decode_ws_multi_locked(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid,
+                                  const uint64_t *stream_off, const uint32_t *stream_len, const uint8_t *in,
+                                  bool must_mask, int64_t max_msg_size, uint64_t max_frames, uint64_t *frame_in_off,
+                                  uint32_t *frame_len, uint64_t *out_off, uint8_t *out, uint8_t *flags_out,
+                                  int32_t *status_out, zmqg_ws_result *results, void *stream)
 {
-    if (!ctx || !results || check_n(n_streams) || check_n(max_frames) || check_n(n_streams * max_frames))
-        return -EINVAL;
     hipStream_t st = (hipStream_t) stream;
-    ZCHECK(ctx, hipSetDevice(ctx->device));
-    if (n_streams == 0)
-        return 0;
-    if (max_frames == 0) {
-        ZCHECK(ctx, hipMemsetAsync(results, 0, n_streams * sizeof *results, st));
-        return 0;
-    }
-    if (!stream_sid || !stream_off || !stream_len || !in || !frame_in_off || !frame_len || !out_off || !out ||
-        !flags_out || !status_out)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
     ZmtpWs &z = ctx->zw;
     const uint64_t slots = n_streams * max_frames;
     int rc;
@@ -3583,6 +3633,30 @@ int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stre
     return decode_batch_impl(ctx, slots, z.sid_fill, frame_in_off, frame_len, must_mask ? out : in, out_off, out,
                              flags_out, status_out, decode_len_bound(max_msg_size, &o), z.fflags, nullptr, nullptr,
                              stream);
+}
+
+int zmqg_decode_ws_multi(zmqg_ctx *ctx, uint64_t n_streams, const uint32_t *stream_sid, const uint64_t *stream_off,
+                         const uint32_t *stream_len, const uint8_t *in, int must_mask, int64_t max_msg_size,
+                         uint64_t max_frames, uint64_t *frame_in_off, uint32_t *frame_len, uint64_t *out_off,
+                         uint8_t *out, uint8_t *flags_out, int32_t *status_out, zmqg_ws_result *results, void *stream)
+{
+    if (!ctx || !results || check_n(n_streams) || check_n(max_frames) || check_n(n_streams * max_frames))
+        return -EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    ZCHECK(ctx, hipSetDevice(ctx->device));
+    if (n_streams == 0)
+        return 0;
+    if (max_frames == 0) {
+        ZCHECK(ctx, hipMemsetAsync(results, 0, n_streams * sizeof *results, st));
+        return 0;
+    }
+    if (!stream_sid || !stream_off || !stream_len || !in || !frame_in_off || !frame_len || !out_off || !out ||
+        !flags_out || !status_out)
+        return -EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return decode_ws_multi_locked(ctx, n_streams, stream_sid, stream_off, stream_len, in, must_mask != 0, max_msg_size,
+                                  max_frames, frame_in_off, frame_len, out_off, out, flags_out, status_out, results,
+                                  stream);
 }
 
 int zmqg_decode_zmtp(zmqg_ctx *ctx, uint32_t sid, const uint8_t *in, uint64_t in_bytes, int64_t max_msg_size,

@@ -177,6 +177,16 @@ class ForwardLb(ctypes.Structure):  # zmqg_forward_lb
                 ("dest_out", _P)]
 
 
+FRAMING_ZMTP, FRAMING_WS, FRAMING_WS_MASKED = 0, 1, 2  # ZMQG_FRAMING_*
+FWD_STATIC, FWD_SUB, FWD_ROUTER, FWD_LB = 0, 1, 2, 3  # ZMQG_FWD_*
+
+
+class ForwardFraming(ctypes.Structure):  # zmqg_forward_framing
+    _fields_ = [("size", _U32), ("reserved", _U32), ("recv", _U32), ("send", _U32), ("mode", _U32),
+                ("reserved2", _U32), ("plan", _P), ("ws_results", _P), ("mask", _P)]
+
+
+_lib.zmqg_forward_framed_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardFraming), _P]
 _lib.zmqg_forward_zmtp_lb_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardLb), _P]
 _lib.zmqg_forward_zmtp_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), _P]
 _lib.zmqg_forward_zmtp_router_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardRouter), _P]
@@ -562,15 +572,21 @@ class CurveContext:
                                      frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
                                      route_dst, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
                                      carry_len, carry_flags, out_bytes)
+        sb = self._subs_plan(sub_idx, sub_off, sub_len, sub_bytes, n_subs, sub_bytes_len, invert, match_out)
+        self._check(_lib.zmqg_forward_zmtp_sub_multi(self._ctx, ctypes.byref(a), ctypes.byref(sb),
+                                                     _stream_handle(stream)), "zmqg_forward_zmtp_sub_multi")
+        del keep
+
+    @staticmethod
+    def _subs_plan(sub_idx=None, sub_off=None, sub_len=None, sub_bytes=None, n_subs=None, sub_bytes_len=None,
+                   invert=False, match_out=None):
+        """The zmqg_forward_subs of forward_zmtp_sub_multi's table arguments."""
         if n_subs is None:
             n_subs = 0 if sub_off is None else int(sub_off.numel())
         if sub_bytes_len is None:
             sub_bytes_len = 0 if sub_bytes is None else int(sub_bytes.numel())
-        sb = ForwardSubs(ctypes.sizeof(ForwardSubs), SUBS_INVERT if invert else 0, int(n_subs), _ptr(sub_idx),
-                         _ptr(sub_off), _ptr(sub_len), _ptr(sub_bytes), int(sub_bytes_len), _ptr(match_out))
-        self._check(_lib.zmqg_forward_zmtp_sub_multi(self._ctx, ctypes.byref(a), ctypes.byref(sb),
-                                                     _stream_handle(stream)), "zmqg_forward_zmtp_sub_multi")
-        del keep
+        return ForwardSubs(ctypes.sizeof(ForwardSubs), SUBS_INVERT if invert else 0, int(n_subs), _ptr(sub_idx),
+                           _ptr(sub_off), _ptr(sub_len), _ptr(sub_bytes), int(sub_bytes_len), _ptr(match_out))
 
     @staticmethod
     def forward_subs_table(prefixes_per_dst):
@@ -717,15 +733,23 @@ class CurveContext:
                                      frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
                                      route_dst, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
                                      carry_len, carry_flags, out_bytes)
+        rt = self._router_plan(flags, src_id_off, src_id_len, id_off, id_len, id_dst, id_bytes, n_ids, id_bytes_len,
+                               dest_out)
+        self._check(_lib.zmqg_forward_zmtp_router_multi(self._ctx, ctypes.byref(a), ctypes.byref(rt),
+                                                        _stream_handle(stream)), "zmqg_forward_zmtp_router_multi")
+        del keep
+
+    @staticmethod
+    def _router_plan(flags, src_id_off=None, src_id_len=None, id_off=None, id_len=None, id_dst=None, id_bytes=None,
+                     n_ids=None, id_bytes_len=None, dest_out=None):
+        """The zmqg_forward_router of forward_zmtp_router_multi's arguments."""
         if n_ids is None:
             n_ids = 0 if id_off is None else int(id_off.numel())
         if id_bytes_len is None:
             id_bytes_len = 0 if id_bytes is None else int(id_bytes.numel())
-        rt = ForwardRouter(ctypes.sizeof(ForwardRouter), int(flags), _ptr(src_id_off), _ptr(src_id_len), int(n_ids),
-                           _ptr(id_off), _ptr(id_len), _ptr(id_dst), _ptr(id_bytes), int(id_bytes_len), _ptr(dest_out))
-        self._check(_lib.zmqg_forward_zmtp_router_multi(self._ctx, ctypes.byref(a), ctypes.byref(rt),
-                                                        _stream_handle(stream)), "zmqg_forward_zmtp_router_multi")
-        del keep
+        return ForwardRouter(ctypes.sizeof(ForwardRouter), int(flags), _ptr(src_id_off), _ptr(src_id_len), int(n_ids),
+                             _ptr(id_off), _ptr(id_len), _ptr(id_dst), _ptr(id_bytes), int(id_bytes_len),
+                             _ptr(dest_out))
 
     @staticmethod
     def forward_lb_pair_base(flags, carry_idx, max_frames, n_streams):
@@ -761,8 +785,18 @@ class CurveContext:
                                      frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, None,
                                      None, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
                                      carry_len, carry_flags, out_bytes)
+        lb, sg = self._lb_plan(int(a.n_streams), flags, stream_group, grp_idx, lb_dst, lb_cur, n_groups, n_lb,
+                               src_id_off, src_id_len, dest_out)
+        self._check(_lib.zmqg_forward_zmtp_lb_multi(self._ctx, ctypes.byref(a), ctypes.byref(lb),
+                                                    _stream_handle(stream)), "zmqg_forward_zmtp_lb_multi")
+        del keep, sg
+
+    @staticmethod
+    def _lb_plan(n_streams, flags, stream_group=None, grp_idx=None, lb_dst=None, lb_cur=None, n_groups=None,
+                 n_lb=None, src_id_off=None, src_id_len=None, dest_out=None):
+        """The zmqg_forward_lb of forward_zmtp_lb_multi's arguments, and the host array it points into."""
         sg = None if stream_group is None else np.ascontiguousarray(stream_group, dtype=np.uint32)
-        if sg is not None and len(sg) != int(a.n_streams):
+        if sg is not None and len(sg) != n_streams:
             raise ValueError("stream_group holds n_streams entries")
         if n_groups is None:
             n_groups = 0 if lb_cur is None else int(lb_cur.numel())
@@ -771,9 +805,47 @@ class CurveContext:
         lb = ForwardLb(ctypes.sizeof(ForwardLb), int(flags), _ptr(src_id_off), _ptr(src_id_len), int(n_groups),
                        sg.ctypes.data if sg is not None and len(sg) else None, _ptr(grp_idx), int(n_lb),
                        _ptr(lb_dst), _ptr(lb_cur), _ptr(dest_out))
-        self._check(_lib.zmqg_forward_zmtp_lb_multi(self._ctx, ctypes.byref(a), ctypes.byref(lb),
-                                                    _stream_handle(stream)), "zmqg_forward_zmtp_lb_multi")
-        del keep, sg
+        return lb, sg
+
+    def forward_framed_multi(self, recv, send, mode, stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames,
+                             frame_in_off, frame_len, plain_off, plain, flags_out, status_out, results, dst_sid,
+                             route_idx, route_dst, out, pair_off, pair_status, dst_results, fwd, ws_results=None,
+                             mask=None, carry_idx=None, carry_off=None, carry_len=None, carry_flags=None, stream=None,
+                             out_bytes=None, **plan):
+        """A forward call with a framing chosen per side
+        (zmqg_forward_framed_multi).  recv / send: FRAMING_ZMTP, FRAMING_WS
+        (unmasked) or FRAMING_WS_MASKED, the framing of the receive buffers
+        and of the send runs.  mode: FWD_STATIC (forward_zmtp_multi's rule),
+        FWD_SUB, FWD_ROUTER or FWD_LB, with that call's own table arguments as
+        keywords (sub_idx ..., flags / id_off ..., flags / stream_group ...;
+        FWD_LB reads no routes: route_idx and route_dst may be None).  With a
+        WebSocket receive side the per-stream results go to ws_results, a
+        device int64 tensor of n_streams x 6 read with ws_results(), and
+        `results` may be None.  With FRAMING_WS_MASKED on the send side, mask
+        is an int32 device tensor of N entries, pair p's 32-bit key value (N
+        from the mode's *_pair_base).  Everything else is the mode's call."""
+        a, keep = self._forward_args(stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
+                                     frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
+                                     route_dst, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
+                                     carry_len, carry_flags, out_bytes)
+        if mode == FWD_STATIC:
+            if plan:
+                raise ValueError("FWD_STATIC takes no table arguments")
+            p = None
+        elif mode == FWD_SUB:
+            p = self._subs_plan(**plan)
+        elif mode == FWD_ROUTER:
+            p = self._router_plan(**plan)
+        elif mode == FWD_LB:
+            p, sg = self._lb_plan(int(a.n_streams), **plan)
+            keep += (sg,)
+        else:
+            raise ValueError("mode is one of FWD_STATIC, FWD_SUB, FWD_ROUTER, FWD_LB")
+        fr = ForwardFraming(ctypes.sizeof(ForwardFraming), 0, int(recv), int(send), int(mode), 0,
+                            None if p is None else ctypes.addressof(p), _ptr(ws_results), _ptr(mask))
+        self._check(_lib.zmqg_forward_framed_multi(self._ctx, ctypes.byref(a), ctypes.byref(fr),
+                                                   _stream_handle(stream)), "zmqg_forward_framed_multi")
+        del keep, p
 
     @staticmethod
     def forward_results(fwd):
