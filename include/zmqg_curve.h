@@ -63,6 +63,9 @@
  *     src/proxy.cpp:90-138,
  *     src/ws_decoder.cpp:39-249,
  *     src/ws_encoder.cpp:26-126                      zmqg_forward_framed_multi
+ *   pipe_t::check_hwm / check_write / write, dist_t::write, router_t::xsend
+ *     src/pipe.cpp:535-541, :207-234,
+ *     src/dist.cpp:196-210, src/router.cpp:185-200   zmqg_forward_credit_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -111,9 +114,12 @@ extern "C" {
  *                   header failure)
  * ZMQG_ERR_BOUND    the frame is longer than zmqg_batch_opts.max_len (the
  *                   caller's promise was broken; the frame is not processed
- *                   and its output region is left as it was) */
+ *                   and its output region is left as it was)
+ * ZMQG_ERR_HWM      zmqg_forward_credit_multi: the pair was live and its
+ *                   destination's credit refused its message */
 #define ZMQG_ERR_SESSION 0x7a000001
 #define ZMQG_ERR_BOUND 0x7a000002
+#define ZMQG_ERR_HWM 0x7a000003
 
 /* msg_t flag bits used on this path (src/msg.hpp:55-62). */
 #define ZMQG_MSG_MORE 1
@@ -841,7 +847,8 @@ int zmqg_forward_zmtp_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, void *
  * does not either); maintaining the table on the device from
  * SUBSCRIBE / CANCEL commands (they stay held commands for the host;
  * zmqg_subs_update_multi, a call of its own, keeps such a table);
- * ZMQ_XPUB_MANUAL, ZMQ_XPUB_NODROP and high-water marks, the welcome message;
+ * ZMQ_XPUB_MANUAL, ZMQ_XPUB_NODROP, the welcome message; high-water marks here
+ * (a subscriber's HWM is zmqg_forward_credit_multi with ZMQG_FWD_SUB);
  * the XSUB upstream direction; WebSocket framing here (it is
  * zmqg_forward_framed_multi with ZMQG_FWD_SUB). */
 #define ZMQG_SUBS_INVERT 1u            /* options.invert_matching: dist_t::reverse_match, src/dist.cpp:64-78 */
@@ -1125,7 +1132,8 @@ int zmqg_subs_update_multi(zmqg_ctx *ctx, const zmqg_subs_update *args, void *st
  * Not offered: ZMQ_ROUTER_MANDATORY and its errors, ZMQ_ROUTER_HANDOVER,
  * ZMQ_ROUTER_RAW; maintaining the id table on the device; DEALER's round-robin
  * choice (lb_t), which is zmqg_forward_zmtp_lb_multi (with its own PREPEND for
- * a ROUTER frontend); high-water marks; WebSocket framing here (it is
+ * a ROUTER frontend); high-water marks here (a full peer's drop is
+ * zmqg_forward_credit_multi with ZMQG_FWD_ROUTER); WebSocket framing here (it is
  * zmqg_forward_framed_multi with ZMQG_FWD_ROUTER); combining with the
  * subscription table. */
 #define ZMQG_ROUTER_PREPEND 1u   /* receive side is a ROUTER: router_t::xrecv */
@@ -1241,7 +1249,9 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
  * is queued when n_groups > 0.
  * Not offered: high-water marks and lb_t's deactivation of a full pipe
  * (src/lb.cpp:103-107): the host keeps a pipe that is not writable out of
- * lb_dst; the exact turn after a membership change (the host edits the range
+ * lb_dst (zmqg_forward_credit_multi, which drops for a full destination in the
+ * other modes, refuses this one: lb_t skips a full pipe, it does not drop); the
+ * exact turn after a membership change (the host edits the range
  * without reading the cursor, the device clamps it); WebSocket framing here
  * (it is zmqg_forward_framed_multi with ZMQG_FWD_LB); combining with the
  * subscription or the id table. */
@@ -1448,6 +1458,102 @@ typedef struct zmqg_forward_framing {   /* 48 bytes */
 } zmqg_forward_framing;
 int zmqg_forward_framed_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
                               const zmqg_forward_framing *framing, void *stream);
+
+/* zmqg_forward_credit_multi: zmqg_forward_framed_multi with a high-water mark
+ * per destination -- what a PUB / XPUB socket does for a subscriber whose pipe
+ * is full (it drops for that one and keeps serving the others) and a ROUTER
+ * without ZMQ_ROUTER_MANDATORY for a full peer (it drops the message).
+ *
+ * The reference counts in whole messages, per pipe:
+ *   pipe_t::check_hwm (src/pipe.cpp:535-541): full when _hwm > 0 and
+ *     _msgs_written - _peers_msgs_read >= _hwm;
+ *   pipe_t::check_write / write (src/pipe.cpp:207-234): _msgs_written rises on
+ *     a part without MORE only, so a multipart message is refused at its first
+ *     part or not at all;
+ *   dist_t::write (src/dist.cpp:196-210, from send_to_matching, :127-142): a
+ *     pipe that refuses a write leaves _matching, _active and _eligible; it
+ *     gets none of the message's further parts and no later message until it
+ *     is re-activated, and the other pipes still get the message;
+ *   router_t::xsend (src/router.cpp:185-200): when the addressed pipe's
+ *     check_write fails, _current_out is dropped and the rest of the message
+ *     discarded.
+ * The peer's read count does not change within a call, so over the messages of
+ * one call this is: at most dst_credit[t] more whole messages for destination
+ * t, everything after that dropped for t alone.  The credit is hwm -
+ * (_msgs_written - _peers_msgs_read), 0 for a pipe that is not writable, and
+ * ZMQG_CREDIT_UNLIMITED for hwm == 0.
+ *
+ * `args` and `framing` are zmqg_forward_framed_multi's and mean what they mean
+ * there; the modes are ZMQG_FWD_STATIC, _SUB and _ROUTER, with either framing
+ * on either side.  Everything that call states holds: the receive side, Q(s),
+ * F, E, fwd[s], the carry, the mode's pair space and N, match_out / dest_out
+ * (they keep describing the routing decision), fit, ENOBUFS, the prefix
+ * property, the nonces in pair order.  One thing changes: which pairs are live.
+ *
+ * Deliveries.  A delivery is (source stream s, forwarded message, route slot
+ * k) with at least one pair that is live under the mode's own rule; all its
+ * live pairs have one destination t.  Its position is p0 = base(s) + slot0 *
+ * d'(s) + k, slot0 the first slot of the outgoing message: the id slot in an
+ * m = 2 pair space, else the head element's slot -- whether or not pair p0 is
+ * itself live (under ZMQG_ROUTER_ROUTE alone it is the consumed address).
+ *
+ * Admission.  The deliveries of destination t are ordered by p0; the i-th
+ * (from 0) is admitted iff i < dst_credit[t] as it stood when the call was
+ * queued, and ZMQG_CREDIT_UNLIMITED admits all.  A stream that names t twice
+ * makes two deliveries and takes two credits.  The count does not look at
+ * dst_sid[t]: a destination with an invalid session still takes credits, and
+ * its pairs report ZMQG_ERR_SESSION as before.
+ *
+ * Outputs.  Every pair of an admitted delivery is the mode's live pair,
+ * unchanged.  Every live pair of a refused delivery becomes not live: it names
+ * no stream, takes no nonce and writes no byte of `out`, its pair_off is
+ * UINT64_MAX and its pair_status (when given) ZMQG_ERR_HWM, which tells an HWM
+ * drop from the other pairs that are not live (ZMQG_ERR_SESSION).  A masked
+ * send side does not read its mask entry.  The other destinations of the same
+ * message are not affected.  For every t < n_dst, with D(t) the deliveries of
+ * t in this call: dst_taken[t] = min(D(t), dst_credit[t]) (D(t) when
+ * unlimited) and dst_dropped[t] = D(t) - dst_taken[t].  taken counts
+ * admissions: a pair that then does not fit is ZMQG_ERR_BOUND and the host's
+ * to send again, as before.  With ZMQG_CREDIT_CONSUME, dst_credit[t] :=
+ * dst_credit[t] - dst_taken[t] (unlimited stays), written behind every read of
+ * the old value; without the flag dst_credit is not written.  dst_credit lives
+ * on the device across calls, like lb_cur: the host adds to it, in stream
+ * order, when a peer's read count comes in.
+ *
+ * Identity.  With every credit ZMQG_CREDIT_UNLIMITED every output of the
+ * framed call is what zmqg_forward_framed_multi produces on the same input,
+ * byte for byte and nonce for nonce, and dst_dropped is all zero.
+ *
+ * Returns -EINVAL, with nothing queued, for a null credit, size !=
+ * sizeof(zmqg_forward_credit), unknown flag bits, mode ZMQG_FWD_LB, n_dst > 0
+ * with a null dst_credit, dst_taken or dst_dropped, and every case of
+ * zmqg_forward_framed_multi.  With n_streams == 0 nothing is done; with N == 0
+ * and n_dst > 0 dst_taken and dst_dropped are zero-filled on the stream and
+ * dst_credit is not written.
+ * Launches: zmqg_forward_framed_multi's, and seven whatever N and n_dst are --
+ * the starts with their counts per tile of pairs, two column passes, the
+ * ranks, the verdict on every pair and the totals in front of the send side,
+ * ZMQG_ERR_HWM behind it (not queued without pair_status) -- and under
+ * ZMQG_FWD_STATIC the heads, which that mode's plan does not need itself.
+ * Not offered: ZMQG_FWD_LB -- lb_t skips a full pipe and swaps it out of the
+ * ring (src/lb.cpp:103-107), so the message goes to the next pipe instead of
+ * being dropped, and every later choice moves with it: a reordering that
+ * depends on the data, where this call only clears pairs (the host keeps a
+ * full pipe out of lb_dst); ZMQ_XPUB_NODROP (src/xpub.cpp:314: one full pipe
+ * refuses the message for all, a dependency across destinations);
+ * ZMQ_ROUTER_MANDATORY's EAGAIN; the low-water mark and re-activation, which
+ * are the host's (it refills dst_credit); limits counted in bytes. */
+#define ZMQG_CREDIT_UNLIMITED 0xffffffffu
+#define ZMQG_CREDIT_CONSUME 1u           /* write dst_credit[t] - dst_taken[t] back (UNLIMITED stays) */
+typedef struct zmqg_forward_credit {     /* 32 bytes */
+    uint32_t size, flags;                /* sizeof(zmqg_forward_credit); 0 or ZMQG_CREDIT_CONSUME */
+    uint32_t *dst_credit;                /* device, n_dst: whole messages t may still take */
+    uint32_t *dst_taken;                 /* device, n_dst, out: deliveries admitted */
+    uint32_t *dst_dropped;               /* device, n_dst, out: deliveries refused */
+} zmqg_forward_credit;
+int zmqg_forward_credit_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
+                              const zmqg_forward_framing *framing,
+                              const zmqg_forward_credit *credit, void *stream);
 
 /* Handshake key derivation in batches, one
  * 32-byte item per thread, items packed back to back:

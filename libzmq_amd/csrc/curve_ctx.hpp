@@ -105,6 +105,11 @@ struct ZmtpWs {
     uint64_t ls_cap = 0;        // and source streams
     DevBuf<uint32_t> s_msgs;    // [ls_cap] the stream's forwarded messages
     DevBuf<uint32_t> s_first;   // [ls_cap] the ring position of its first message
+    uint64_t k_cap = 0;         // zmqg_forward_credit_multi: pairs
+    DevBuf<uint32_t> p_key;     // [k_cap] at a delivery's first pair: its destination (else none)
+    DevBuf<uint32_t> p_rank;    // [k_cap] and its rank among that destination's deliveries
+    DevBuf<uint8_t> p_hwm;      // [k_cap] the pair was live and its delivery was refused
+    DevBuf<uint32_t> k_tab;     // [tiles][destinations], [row blocks][destinations], totals [destinations]
     uint64_t u_cap = 0;         // zmqg_subs_update_multi: events (cleared slots, then the decode call's slots)
     DevBuf<uint32_t> u_h0;      // [u_cap] the slots holding the event's topic at call start
     DevBuf<int8_t> u_delta;     // [u_cap] what the event did to its destination's hold on the topic: +1 / -1 / 0

@@ -3,6 +3,7 @@
 // zmqg_curve.hip, included there after the receive and send sides it queues.
 #pragma once
 #include "curve_fwd_common.hpp"
+#include "curve_fwd_credit.hpp"
 
 static_assert(kFwdNoStream == kZsendNoSession, "curve_fwd_common.hpp restates the send side's value");
 
@@ -27,6 +28,7 @@ struct FwdCall {
     FwdTab tab;
     FwdSrc src;
     FwdPairsOut out;
+    const zmqg_forward_credit *credit = nullptr; // zmqg_forward_credit_multi: the pass in front of the send side
     bool empty() const { return a->n_streams == 0; } // nothing to queue
 };
 
@@ -130,27 +132,99 @@ static int forward_send(zmqg_ctx *ctx, const FwdCall &c, const uint32_t *mask)
                                    a.dst_results, c.st);
 }
 
-static int forward_finish(zmqg_ctx *ctx, const FwdCall &c)
+// The pair space of the plan, as zmqg_forward_credit_multi's pass reads it
+// (FwdCreditSpace, curve_fwd_credit.hpp, without the arrays)
+struct FwdCreditMode {
+    bool twice, one_route, addr;
+};
+
+// zmqg_forward_credit_multi between the plan and the send side: the starts and
+// their counts per tile, the column passes, the ranks, the verdict on every
+// pair, the totals (curve_fwd_credit.hpp).  Without pairs the totals are zeros.
+static int fwd_credit_pass(zmqg_ctx *ctx, const FwdCall &c, const FwdCreditMode &cm)
+{
+    const zmqg_forward_credit &cr = *c.credit;
+    ZmtpWs &z = ctx->zw;
+    const uint32_t N = (uint32_t) c.t.N, D = (uint32_t) c.a->n_dst;
+    if (D == 0)
+        return 0;
+    if (N == 0) {
+        ZCHECK(ctx, hipMemsetAsync(cr.dst_taken, 0, 4 * (size_t) D, c.st));
+        ZCHECK(ctx, hipMemsetAsync(cr.dst_dropped, 0, 4 * (size_t) D, c.st));
+        return 0;
+    }
+    const uint32_t T = zsend_tile_frames(N, D); // (kFwdCreditTile until the table outgrows its bounds)
+    const uint32_t tiles = (N + T - 1) / T, rbs = (tiles + kFwdCreditRB - 1) / kFwdCreditRB;
+    int rc;
+    if ((rc = reserve_group(ctx, c.st, "p_key..p_hwm", z.k_cap, 1024, N, z.p_key, z.p_rank, z.p_hwm)))
+        return rc;
+    const size_t need = ((size_t) tiles + rbs + 1) * D; // counts, block sums, totals
+    ZRESERVE(ctx, z.k_tab, grown_cap(z.k_tab.count, 4096, need), c.st);
+    uint32_t *cnt = z.k_tab, *blk = cnt + (size_t) tiles * D, *tot = blk + (size_t) rbs * D;
+    const FwdCreditSpace sp = {cm.twice, cm.one_route, cm.addr, z.e_head.p, z.e_verdict.p};
+    const dim3 cg((D + 255) / 256, rbs), pg((N + 255) / 256);
+    hipLaunchKernelGGL(k_fwd_credit_tiles, dim3(tiles), dim3(256), D * sizeof(uint32_t), c.st, N, T, D, c.src, c.tab,
+                       sp, (const uint32_t *) c.out.p_stream, z.p_key.p, cnt, tot);
+    ZCHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fwd_credit_colblk, cg, dim3(256), 0, c.st, tiles, D, (const uint32_t *) cnt, blk, tot);
+    ZCHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fwd_credit_colscan, cg, dim3(256), 0, c.st, tiles, D, cnt, (const uint32_t *) blk);
+    ZCHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fwd_credit_ranks, dim3(tiles), dim3(kFwdCreditThreads), D * sizeof(uint32_t), c.st, N, T, D,
+                       (const uint32_t *) z.p_key.p, (const uint32_t *) cnt, z.p_rank.p);
+    ZCHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fwd_credit_apply, pg, dim3(256), 0, c.st, N, D, c.src, c.tab, sp,
+                       (const uint32_t *) z.p_key.p, (const uint32_t *) z.p_rank.p,
+                       (const uint32_t *) cr.dst_credit, c.out, z.p_hwm.p);
+    ZCHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fwd_credit_totals, dim3((D + 255) / 256), dim3(256), 0, c.st, D, (const uint32_t *) tot,
+                       cr.dst_credit, cr.dst_taken, cr.dst_dropped, cr.flags & ZMQG_CREDIT_CONSUME);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+// The send side; in front of it zmqg_forward_credit_multi's pass, and behind it
+// ZMQG_ERR_HWM for the pairs the pass cleared
+static int forward_finish(zmqg_ctx *ctx, const FwdCall &c, const FwdCreditMode &cm = FwdCreditMode())
 {
     const zmqg_forward_zmtp &a = *c.a;
+    int rc;
+    if (c.credit && (rc = fwd_credit_pass(ctx, c, cm)))
+        return rc;
     if (a.n_dst == 0) {
         ZCHECK(ctx, hipMemsetAsync(a.pair_off, 0, sizeof(uint64_t), c.st));
         return 0;
     }
     if (c.fr.send == ZMQG_FRAMING_WS_MASKED)
-        return forward_send<kZsendWsMasked>(ctx, c, c.fr.mask);
-    if (c.fr.send == ZMQG_FRAMING_WS)
-        return forward_send<kZsendWs>(ctx, c, nullptr);
-    return forward_send<kZsendZmtp>(ctx, c, nullptr);
+        rc = forward_send<kZsendWsMasked>(ctx, c, c.fr.mask);
+    else if (c.fr.send == ZMQG_FRAMING_WS)
+        rc = forward_send<kZsendWs>(ctx, c, nullptr);
+    else
+        rc = forward_send<kZsendZmtp>(ctx, c, nullptr);
+    if (rc || !c.credit || !a.pair_status || c.t.N == 0)
+        return rc;
+    hipLaunchKernelGGL(k_fwd_credit_status, dim3((unsigned) ((c.t.N + 255) / 256)), dim3(256), 0, c.st,
+                       (uint32_t) c.t.N, (const uint8_t *) ctx->zw.p_hwm.p, a.pair_status);
+    ZCHECK(ctx, hipGetLastError());
+    return 0;
 }
 
-// zmqg_forward_zmtp_multi: the pairs (one lane per pair)
+// zmqg_forward_zmtp_multi: the pairs (one lane per pair); in front of them, for
+// zmqg_forward_credit_multi alone, the heads (the table then has its ebase row)
 static int fwd_plan_static(zmqg_ctx *ctx, const FwdCall &c)
 {
-    const uint64_t N = c.t.N;
+    ZmtpWs &z = ctx->zw;
+    const uint64_t S = c.src.n_streams, N = c.t.N;
     int rc;
+    if (c.credit && (rc = reserve_group(ctx, c.st, "e_head", z.e_cap, 1024, c.t.EN, z.e_head)))
+        return rc;
     if ((rc = forward_receive(ctx, c)) || N == 0)
         return rc;
+    if (c.credit) {
+        hipLaunchKernelGGL(k_fwd_heads<false>, dim3(wave_grid(S, kFwdThreads)), dim3(kFwdThreads), 0, c.st, c.src,
+                           c.tab, z.e_head.p, nullptr, nullptr);
+        ZCHECK(ctx, hipGetLastError());
+    }
     hipLaunchKernelGGL(k_fwd_pairs<false>, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, c.st, (uint32_t) N, c.src,
                        c.tab, c.out, nullptr, nullptr, nullptr);
     ZCHECK(ctx, hipGetLastError());

@@ -3359,10 +3359,13 @@ static int decode_ws_multi_locked(zmqg_ctx *ctx, uint64_t n_streams, const uint3
 
 // The four routing rules, each with the framing of its two sides: the entry of
 // its own name passes ZMTP on both, zmqg_forward_framed_multi the caller's.
-static int forward_static(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const FwdFraming &fr, void *stream)
+// (credit, here and below: zmqg_forward_credit_multi's struct, checked there; NULL for every other entry)
+static int forward_static(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const FwdFraming &fr, void *stream,
+                          const zmqg_forward_credit *credit = nullptr)
 {
-    const FwdTableIn in = {args, false, false, 1u, nullptr, 0};
+    const FwdTableIn in = {args, false, credit != nullptr, 1u, nullptr, 0}; // (the credit pass reads the heads)
     FwdCall c;
+    c.credit = credit;
     int rc;
     if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_static(ctx, c)))
         return rc;
@@ -3372,7 +3375,7 @@ static int forward_static(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const Fw
 // The table's launch-free checks; what the host cannot see (sub_idx's entries,
 // the subscriptions' extents) the match kernel bounds itself.
 static int forward_sub(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_subs *subs,
-                       const FwdFraming &fr, void *stream)
+                       const FwdFraming &fr, void *stream, const zmqg_forward_credit *credit = nullptr)
 {
     if (!ctx || !args || !subs || subs->size != sizeof *subs || (subs->flags & ~ZMQG_SUBS_INVERT) != 0)
         return -EINVAL;
@@ -3381,6 +3384,7 @@ static int forward_sub(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_
         return -EINVAL;
     const FwdTableIn in = {args, false, true, 1u, nullptr, 0};
     FwdCall c;
+    c.credit = credit;
     int rc;
     if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_sub(ctx, c, *subs)))
         return rc;
@@ -3390,7 +3394,7 @@ static int forward_sub(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_
 // The router struct's launch-free checks; the id table's contents the lookup
 // bounds itself (curve_fwd_route.hpp).  flags == 0 is zmqg_forward_zmtp_multi.
 static int forward_router(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_router *router,
-                          const FwdFraming &fr, void *stream)
+                          const FwdFraming &fr, void *stream, const zmqg_forward_credit *credit = nullptr)
 {
     if (!ctx || !args || !router || router->size != sizeof *router ||
         (router->flags & ~(ZMQG_ROUTER_PREPEND | ZMQG_ROUTER_ROUTE)) != 0)
@@ -3403,14 +3407,16 @@ static int forward_router(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zm
          (router->id_bytes_len > 0 && !router->id_bytes)))
         return -EINVAL;
     if (!router->flags)
-        return forward_static(ctx, args, fr, stream);
+        return forward_static(ctx, args, fr, stream, credit);
     // ROUTE: one route slot a stream; PREPEND alone: an id slot in front of every element
     const FwdTableIn in = {args, route, true, prepend && !route ? 2u : 1u, nullptr, 0};
     FwdCall c;
+    c.credit = credit;
     int rc;
     if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_router(ctx, c, *router)))
         return rc;
-    return forward_finish(ctx, c);
+    // (ROUTE alone: a message starts at its consumed address, and the verdict names its destination)
+    return forward_finish(ctx, c, FwdCreditMode{prepend && !route, route, route && !prepend});
 }
 
 // The load balancer's launch-free checks: the struct, and stream_group, the one
@@ -3466,9 +3472,9 @@ int zmqg_forward_zmtp_lb_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, con
 
 // The framing struct's launch-free checks, then the mode's rule with its own;
 // what depends on the sizes (ws_results with streams, mask with pairs) is
-// forward_begin's.
-int zmqg_forward_framed_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_framing *framing,
-                              void *stream)
+// forward_begin's.  credit: zmqg_forward_credit_multi's struct, checked there.
+static int forward_framed(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_framing *framing,
+                          const zmqg_forward_credit *credit, void *stream)
 {
     if (!ctx || !args || !framing || framing->size != sizeof *framing || framing->reserved != 0 ||
         framing->reserved2 != 0)
@@ -3482,14 +3488,37 @@ int zmqg_forward_framed_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
                            framing->send == ZMQG_FRAMING_WS_MASKED ? framing->mask : nullptr};
     switch (framing->mode) {
     case ZMQG_FWD_SUB:
-        return forward_sub(ctx, args, (const zmqg_forward_subs *) framing->plan, fr, stream);
+        return forward_sub(ctx, args, (const zmqg_forward_subs *) framing->plan, fr, stream, credit);
     case ZMQG_FWD_ROUTER:
-        return forward_router(ctx, args, (const zmqg_forward_router *) framing->plan, fr, stream);
-    case ZMQG_FWD_LB:
+        return forward_router(ctx, args, (const zmqg_forward_router *) framing->plan, fr, stream, credit);
+    case ZMQG_FWD_LB: // (no credit: zmqg_forward_credit_multi refuses the mode)
         return forward_lb(ctx, args, (const zmqg_forward_lb *) framing->plan, fr, stream);
     default:
-        return forward_static(ctx, args, fr, stream);
+        return forward_static(ctx, args, fr, stream, credit);
     }
+}
+
+int zmqg_forward_framed_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_framing *framing,
+                              void *stream)
+{
+    return forward_framed(ctx, args, framing, nullptr, stream);
+}
+
+// The credit struct's launch-free checks, then the framed call with the pass
+// between its plan and its send side (curve_fwd_credit.hpp).  The load balancer
+// skips a full pipe and goes on to the next (src/lb.cpp:103-107): a reordering
+// that depends on the data, not a drop, and not offered.
+int zmqg_forward_credit_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_framing *framing,
+                              const zmqg_forward_credit *credit, void *stream)
+{
+    if (!ctx || !args || !framing || !credit || credit->size != sizeof *credit ||
+        (credit->flags & ~ZMQG_CREDIT_CONSUME) != 0)
+        return -EINVAL;
+    if (framing->size != sizeof *framing || framing->mode == ZMQG_FWD_LB || args->size != sizeof *args)
+        return -EINVAL;
+    if (args->n_dst > 0 && (!credit->dst_credit || !credit->dst_taken || !credit->dst_dropped))
+        return -EINVAL;
+    return forward_framed(ctx, args, framing, credit, stream);
 }
 
 // The launch-free checks, the two host arrays through the pinned staging, then

@@ -40,6 +40,7 @@ HS_HELLO_BYTES, HS_CLIENT_STATE_BYTES = 200, 128
 # library codes (zmqg_curve.h): unknown session; frame above the caller's max_len
 ERR_SESSION = 0x7A000001
 ERR_BOUND = 0x7A000002
+ERR_HWM = 0x7A000003
 # the largest max_len for which a call skips the large-frame kernels
 MAX_LEN_FRAME_KERNEL_DECODE = 4608
 MAX_LEN_FRAME_KERNEL_ENCODE = 4565
@@ -186,6 +187,15 @@ class ForwardFraming(ctypes.Structure):  # zmqg_forward_framing
                 ("reserved2", _U32), ("plan", _P), ("ws_results", _P), ("mask", _P)]
 
 
+CREDIT_UNLIMITED, CREDIT_CONSUME = 0xffffffff, 1  # ZMQG_CREDIT_*
+
+
+class ForwardCredit(ctypes.Structure):  # zmqg_forward_credit
+    _fields_ = [("size", _U32), ("flags", _U32), ("dst_credit", _P), ("dst_taken", _P), ("dst_dropped", _P)]
+
+
+_lib.zmqg_forward_credit_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardFraming),
+                                           ctypes.POINTER(ForwardCredit), _P]
 _lib.zmqg_forward_framed_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardFraming), _P]
 _lib.zmqg_forward_zmtp_lb_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardLb), _P]
 _lib.zmqg_forward_zmtp_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), _P]
@@ -824,6 +834,20 @@ class CurveContext:
         `results` may be None.  With FRAMING_WS_MASKED on the send side, mask
         is an int32 device tensor of N entries, pair p's 32-bit key value (N
         from the mode's *_pair_base).  Everything else is the mode's call."""
+        a, fr, keep = self._framed_args(recv, send, mode, stream_sid, stream_off, stream_len, inp, max_msg_size,
+                                        max_frames, frame_in_off, frame_len, plain_off, plain, flags_out, status_out,
+                                        results, dst_sid, route_idx, route_dst, out, pair_off, pair_status,
+                                        dst_results, fwd, ws_results, mask, carry_idx, carry_off, carry_len,
+                                        carry_flags, out_bytes, plan)
+        self._check(_lib.zmqg_forward_framed_multi(self._ctx, ctypes.byref(a), ctypes.byref(fr),
+                                                   _stream_handle(stream)), "zmqg_forward_framed_multi")
+        del keep
+
+    def _framed_args(self, recv, send, mode, stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames,
+                     frame_in_off, frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
+                     route_dst, out, pair_off, pair_status, dst_results, fwd, ws_results, mask, carry_idx, carry_off,
+                     carry_len, carry_flags, out_bytes, plan):
+        """The zmqg_forward_zmtp and zmqg_forward_framing of a framed call, and what they point into."""
         a, keep = self._forward_args(stream_sid, stream_off, stream_len, inp, max_msg_size, max_frames, frame_in_off,
                                      frame_len, plain_off, plain, flags_out, status_out, results, dst_sid, route_idx,
                                      route_dst, out, pair_off, pair_status, dst_results, fwd, carry_idx, carry_off,
@@ -843,9 +867,34 @@ class CurveContext:
             raise ValueError("mode is one of FWD_STATIC, FWD_SUB, FWD_ROUTER, FWD_LB")
         fr = ForwardFraming(ctypes.sizeof(ForwardFraming), 0, int(recv), int(send), int(mode), 0,
                             None if p is None else ctypes.addressof(p), _ptr(ws_results), _ptr(mask))
-        self._check(_lib.zmqg_forward_framed_multi(self._ctx, ctypes.byref(a), ctypes.byref(fr),
-                                                   _stream_handle(stream)), "zmqg_forward_framed_multi")
-        del keep, p
+        return a, fr, keep + (p,)
+
+    def forward_credit_multi(self, recv, send, mode, dst_credit, dst_taken, dst_dropped, stream_sid, stream_off,
+                             stream_len, inp, max_msg_size, max_frames, frame_in_off, frame_len, plain_off, plain,
+                             flags_out, status_out, results, dst_sid, route_idx, route_dst, out, pair_off, pair_status,
+                             dst_results, fwd, consume=False, ws_results=None, mask=None, carry_idx=None,
+                             carry_off=None, carry_len=None, carry_flags=None, stream=None, out_bytes=None, **plan):
+        """forward_framed_multi with a high-water mark per destination
+        (zmqg_forward_credit_multi): destination t takes at most dst_credit[t]
+        more whole messages in this call (CREDIT_UNLIMITED: all), in pair
+        order; the pairs of a refused message are not sent and report ERR_HWM
+        in pair_status, for that destination alone.  dst_credit, dst_taken and
+        dst_dropped are int32 device tensors of n_dst entries; taken / dropped
+        receive the admitted / refused messages per destination, and with
+        consume=True dst_credit is left holding what remains.  dst_credit
+        lives on the device across calls; the host adds to it on the stream
+        when a peer has read.  mode: FWD_STATIC, FWD_SUB or FWD_ROUTER.
+        Everything else is forward_framed_multi's."""
+        a, fr, keep = self._framed_args(recv, send, mode, stream_sid, stream_off, stream_len, inp, max_msg_size,
+                                        max_frames, frame_in_off, frame_len, plain_off, plain, flags_out, status_out,
+                                        results, dst_sid, route_idx, route_dst, out, pair_off, pair_status,
+                                        dst_results, fwd, ws_results, mask, carry_idx, carry_off, carry_len,
+                                        carry_flags, out_bytes, plan)
+        cr = ForwardCredit(ctypes.sizeof(ForwardCredit), CREDIT_CONSUME if consume else 0, _ptr(dst_credit),
+                           _ptr(dst_taken), _ptr(dst_dropped))
+        self._check(_lib.zmqg_forward_credit_multi(self._ctx, ctypes.byref(a), ctypes.byref(fr), ctypes.byref(cr),
+                                                   _stream_handle(stream)), "zmqg_forward_credit_multi")
+        del keep
 
     @staticmethod
     def forward_results(fwd):
