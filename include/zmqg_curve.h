@@ -66,6 +66,9 @@
  *   pipe_t::check_hwm / check_write / write, dist_t::write, router_t::xsend
  *     src/pipe.cpp:535-541, :207-234,
  *     src/dist.cpp:196-210, src/router.cpp:185-200   zmqg_forward_credit_multi
+ *   lb_t::sendpipe with pipes that refuse a write
+ *     src/lb.cpp:56-131 (:103-107),
+ *     src/pipe.cpp:207-220, :535-541                 zmqg_forward_lb_credit_multi
  *
  * One call processes a batch of independent MESSAGE frames.  Each frame
  * belongs to a session (one CURVE connection = one curve_encoding_t).  The
@@ -116,7 +119,9 @@ extern "C" {
  *                   caller's promise was broken; the frame is not processed
  *                   and its output region is left as it was)
  * ZMQG_ERR_HWM      zmqg_forward_credit_multi: the pair was live and its
- *                   destination's credit refused its message */
+ *                   destination's credit refused its message;
+ *                   zmqg_forward_lb_credit_multi: the pair's message found
+ *                   every entry of its group's ring full */
 #define ZMQG_ERR_SESSION 0x7a000001
 #define ZMQG_ERR_BOUND 0x7a000002
 #define ZMQG_ERR_HWM 0x7a000003
@@ -1250,8 +1255,9 @@ int zmqg_forward_zmtp_router_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
  * Not offered: high-water marks and lb_t's deactivation of a full pipe
  * (src/lb.cpp:103-107): the host keeps a pipe that is not writable out of
  * lb_dst (zmqg_forward_credit_multi, which drops for a full destination in the
- * other modes, refuses this one: lb_t skips a full pipe, it does not drop); the
- * exact turn after a membership change (the host edits the range
+ * other modes, refuses this one: lb_t skips a full pipe, it does not drop;
+ * zmqg_forward_lb_credit_multi is this call with that skip made on the
+ * device); the exact turn after a membership change (the host edits the range
  * without reading the cursor, the device clamps it); WebSocket framing here
  * (it is zmqg_forward_framed_multi with ZMQG_FWD_LB); combining with the
  * subscription or the id table. */
@@ -1539,7 +1545,8 @@ int zmqg_forward_framed_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
  * ring (src/lb.cpp:103-107), so the message goes to the next pipe instead of
  * being dropped, and every later choice moves with it: a reordering that
  * depends on the data, where this call only clears pairs (the host keeps a
- * full pipe out of lb_dst); ZMQ_XPUB_NODROP (src/xpub.cpp:314: one full pipe
+ * full pipe out of lb_dst, or calls zmqg_forward_lb_credit_multi, which makes
+ * that choice on the device); ZMQ_XPUB_NODROP (src/xpub.cpp:314: one full pipe
  * refuses the message for all, a dependency across destinations);
  * ZMQ_ROUTER_MANDATORY's EAGAIN; the low-water mark and re-activation, which
  * are the host's (it refills dst_credit); limits counted in bytes. */
@@ -1554,6 +1561,112 @@ typedef struct zmqg_forward_credit {     /* 32 bytes */
 int zmqg_forward_credit_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
                               const zmqg_forward_framing *framing,
                               const zmqg_forward_credit *credit, void *stream);
+
+/* zmqg_forward_lb_credit_multi: zmqg_forward_framed_multi with ZMQG_FWD_LB
+ * under per-destination high-water marks -- what a PUSH or a DEALER socket does
+ * for a worker whose pipe is full.  lb_t does not drop (lb_t::sendpipe,
+ * src/lb.cpp:56-131): when _pipes[_current] refuses the write
+ * (pipe_t::check_write / check_hwm, src/pipe.cpp:207-220, src/pipe.cpp:535-541)
+ * it takes the pipe out of the active range -- _active--, then the pipe at
+ * _current and the one at _active change places, or _current = 0 when there is
+ * nothing to swap (src/lb.cpp:103-107) -- and offers the message to the next
+ * one.  PUSH/PULL pipelines and ROUTER/DEALER worker pools rely on that to keep
+ * a slow worker from being overrun.  The host cannot prepare the ring for it:
+ * how many messages a receive buffer holds is known after the decode only.
+ *
+ * `args` and `framing` are zmqg_forward_framed_multi's; framing->mode must be
+ * ZMQG_FWD_LB and framing->plan a zmqg_forward_lb.  `credit` is
+ * zmqg_forward_credit_multi's struct, unchanged.  Either framing on either side
+ * and ZMQG_LB_PREPEND work as in the framed call.  Everything that call states
+ * for ZMQG_FWD_LB holds: the receive side, Q(s), F, E, fwd[s], the carry, the
+ * pair space with m = 1 or 2, N, the group table and its clamps, the order of a
+ * group's messages (streams rising, elements rising), fit, ENOBUFS, the prefix
+ * property, the nonces in pair order.  Two things change: the choice, and the
+ * cursor after the call.
+ *
+ * State of group g when the call is queued.  The working ring R[0 .. A) is a
+ * copy of lb_dst[lo .. lo + A0), lo and A0 the group's clamped range; the call
+ * never writes lb_dst.  cur = cur0(g).  Ring position j has a working credit
+ * w[j] = dst_credit[R[j]] as it stood when the call was queued.
+ * ZMQG_CREDIT_UNLIMITED never runs out.  An entry that names no destination
+ * (R[j] >= n_dst) never runs out either: it keeps taking its turn, as in
+ * zmqg_forward_zmtp_lb_multi.
+ *
+ * Choice.  Per message, in the group's order:
+ *     while A > 0:
+ *         if w[cur] is unlimited or > 0:
+ *             the message goes to R[cur]; a finite w[cur] drops by one
+ *             if ++cur >= A: cur = 0
+ *             break
+ *         A -= 1                                   (src/lb.cpp:103-107)
+ *         if cur < A: swap entries cur and A (R and w together)
+ *         else:       cur = 0
+ *     if no entry took it (A == 0): the message is refused
+ * Admission is per whole message, at its head: _msgs_written rises on a part
+ * without MORE only (pipe_t::write, src/pipe.cpp:222-234), so the later parts
+ * of an admitted message always pass.  Only whole messages are forwarded, so
+ * lb_t's _more / _dropping branch (src/lb.cpp:78-101), which discards the rest
+ * of a message whose pipe went away between its parts, cannot arise.
+ *
+ * Outputs.  An admitted message has the LB call's live pairs, unchanged:
+ * dest_out = t, the entry's value, and when t names no destination
+ * ZMQG_LB_NO_PEER with pair_status ZMQG_ERR_SESSION as there.  A refused
+ * message -- every entry of the ring was deactivated in this call -- has no live
+ * pair: every slot of its elements, and the id slot in front of its head, names
+ * no stream, takes no nonce, writes no byte of `out`, reads no mask entry; its
+ * pair_off is UINT64_MAX, its dest_out ZMQG_LB_NO_PEER and its pair_status
+ * (when given) ZMQG_ERR_HWM.  The message is whole in `plain`, and the host
+ * re-offers it as a carry once a peer has read.  A stream without a group, and
+ * a range that was empty from the start, report ZMQG_ERR_SESSION as in the LB
+ * call.
+ * lb_cur[g] after the call is the original ring position (the index into the
+ * group's range of lb_dst) of the entry the working cursor points at after the
+ * last message, or 0 when A ended at 0.  With no deactivation that is (cur0 +
+ * M(g)) mod A, the LB call's value.  The permuted ring does not outlive the
+ * call: a later call starts from lb_dst as the host keeps it, and finds an
+ * entry whose credit is still 0 full again.  The exact turn after a
+ * deactivation is therefore lb_t's within a call and approximate across calls,
+ * like the turn after a membership change in zmqg_forward_zmtp_lb_multi.
+ * Counts.  X(t) is the number of messages sent to t < n_dst in this call.
+ * dst_taken[t] = min(X(t), dst_credit[t]) (X(t) when unlimited), dst_dropped[t]
+ * = X(t) - dst_taken[t]; with ZMQG_CREDIT_CONSUME dst_credit[t] := dst_credit[t]
+ * - dst_taken[t] (unlimited stays), written in a launch behind every read of
+ * the old value; without the flag dst_credit is not written.  taken counts
+ * admissions: a pair that then does not fit is ZMQG_ERR_BOUND and the host's to
+ * send again.  When every destination is named by at most one ring entry over
+ * all groups -- all that lb_t can have -- X(t) <= dst_credit[t] and dst_dropped
+ * is all zero: refused messages are not counted against any destination.  A
+ * destination named by several entries is counted per entry, each with the
+ * whole credit; it may then be sent more than its credit: dst_dropped shows
+ * the excess, and the write-back saturates at 0.  That is defined and
+ * memory-safe.
+ *
+ * Identity.  With every credit ZMQG_CREDIT_UNLIMITED every output equals
+ * zmqg_forward_framed_multi's with ZMQG_FWD_LB on the same input, byte for byte
+ * and nonce for nonce, lb_cur included.
+ *
+ * Returns -EINVAL, with nothing queued, for a null credit, size !=
+ * sizeof(zmqg_forward_credit), unknown flag bits, a mode other than
+ * ZMQG_FWD_LB, n_dst > 0 with a null dst_credit, dst_taken or dst_dropped, and
+ * every case of zmqg_forward_framed_multi with ZMQG_FWD_LB.  With n_streams ==
+ * 0 nothing is done.  With N == 0 and n_dst > 0 dst_taken and dst_dropped are
+ * zero-filled on the stream, dst_credit is not written and lb_cur is clamped as
+ * in the LB call.  A grp_idx that does not rise can make two groups' ranges
+ * overlap: all accesses stay in bounds, and the outcome of the overlapping
+ * groups is unspecified.
+ * Launches: the framed LB call's -- with the groups' launch one workgroup per
+ * group, walking the group in epochs between deactivations (at most A0 + 1 of
+ * them), and the pairs' launch reading its result -- and three more whatever the
+ * sizes are: a memset of the counts X in front, the totals, and ZMQG_ERR_HWM
+ * behind the send side (not queued without pair_status).
+ * Not offered: persisting the permuted ring or an _active count across calls;
+ * lb_t::has_out's eager deactivation; ZMQ_XPUB_NODROP, ZMQ_ROUTER_MANDATORY;
+ * the low-water mark and re-activation, which are the host's (it refills
+ * dst_credit); limits counted in bytes; compacting the pairs that are not live
+ * before the encode. */
+int zmqg_forward_lb_credit_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args,
+                                 const zmqg_forward_framing *framing,
+                                 const zmqg_forward_credit *credit, void *stream);
 
 /* Handshake key derivation in batches, one
  * 32-byte item per thread, items packed back to back:

@@ -110,6 +110,12 @@ struct ZmtpWs {
     DevBuf<uint32_t> p_rank;    // [k_cap] and its rank among that destination's deliveries
     DevBuf<uint8_t> p_hwm;      // [k_cap] the pair was live and its delivery was refused
     DevBuf<uint32_t> k_tab;     // [tiles][destinations], [row blocks][destinations], totals [destinations]
+    uint64_t lc_cap = 0;        // zmqg_forward_lb_credit_multi: elements
+    DevBuf<uint32_t> e_pick;    // [lc_cap] at ebase[s] + i: where stream s's i-th message goes, or refused
+    uint64_t lr_cap = 0;        // and ring entries (n_lb), at each group's absolute positions
+    DevBuf<uint32_t> r_orig;    // [lr_cap] the working ring: each entry's original position in its group
+    DevBuf<uint32_t> r_w;       // [lr_cap] and its working credit
+    DevBuf<uint32_t> x_tot;     // [destinations] the messages sent to each
     uint64_t u_cap = 0;         // zmqg_subs_update_multi: events (cleared slots, then the decode call's slots)
     DevBuf<uint32_t> u_h0;      // [u_cap] the slots holding the event's topic at call start
     DevBuf<int8_t> u_delta;     // [u_cap] what the event did to its destination's hold on the topic: +1 / -1 / 0

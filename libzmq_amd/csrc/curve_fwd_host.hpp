@@ -4,6 +4,7 @@
 #pragma once
 #include "curve_fwd_common.hpp"
 #include "curve_fwd_credit.hpp"
+#include "curve_fwd_lb_credit.hpp"
 
 static_assert(kFwdNoStream == kZsendNoSession, "curve_fwd_common.hpp restates the send side's value");
 
@@ -29,6 +30,7 @@ struct FwdCall {
     FwdSrc src;
     FwdPairsOut out;
     const zmqg_forward_credit *credit = nullptr; // zmqg_forward_credit_multi: the pass in front of the send side
+    bool credit_in_plan = false; // zmqg_forward_lb_credit_multi: the plan has applied the credits itself, no pass
     bool empty() const { return a->n_streams == 0; } // nothing to queue
 };
 
@@ -184,12 +186,13 @@ static int fwd_credit_pass(zmqg_ctx *ctx, const FwdCall &c, const FwdCreditMode 
 }
 
 // The send side; in front of it zmqg_forward_credit_multi's pass, and behind it
-// ZMQG_ERR_HWM for the pairs the pass cleared
+// ZMQG_ERR_HWM for the pairs the pass cleared (or, for
+// zmqg_forward_lb_credit_multi, the pairs the plan left without a destination)
 static int forward_finish(zmqg_ctx *ctx, const FwdCall &c, const FwdCreditMode &cm = FwdCreditMode())
 {
     const zmqg_forward_zmtp &a = *c.a;
     int rc;
-    if (c.credit && (rc = fwd_credit_pass(ctx, c, cm)))
+    if (c.credit && !c.credit_in_plan && (rc = fwd_credit_pass(ctx, c, cm)))
         return rc;
     if (a.n_dst == 0) {
         ZCHECK(ctx, hipMemsetAsync(a.pair_off, 0, sizeof(uint64_t), c.st));
@@ -322,5 +325,64 @@ static int fwd_plan_lb(zmqg_ctx *ctx, const FwdCall &c, const zmqg_forward_lb &l
                            lb.dest_out);
         ZCHECK(ctx, hipGetLastError());
     }
+    return 0;
+}
+
+// zmqg_forward_lb_credit_multi: fwd_plan_lb with the choice made under the
+// credits (curve_fwd_lb_credit.hpp): the heads, one workgroup per group for the
+// epochs, the pairs, the totals.  X(t) is zeroed on the stream in front of them.
+// Without pairs the totals are zeros and k_fwd_lb_groups clamps the cursors.
+static int fwd_plan_lb_credit(zmqg_ctx *ctx, const FwdCall &c, const zmqg_forward_lb &lb)
+{
+    ZmtpWs &z = ctx->zw;
+    const zmqg_forward_credit &cr = *c.credit;
+    const uint64_t S = c.src.n_streams, G = lb.n_groups, N = c.t.N, EN = c.t.EN;
+    const uint32_t D = (uint32_t) c.a->n_dst;
+    const uint32_t *sgrp = c.tab.rdst, *gidx = sgrp + S, *gstr = gidx + (G + 1);
+    int rc;
+    if ((rc = reserve_group(ctx, c.st, "e_rank", z.l_cap, 1024, EN, z.e_rank)) ||
+        (rc = reserve_group(ctx, c.st, "s_msgs, s_first", z.ls_cap, 1024, S, z.s_msgs, z.s_first)) ||
+        (rc = reserve_group(ctx, c.st, "e_head", z.e_cap, 1024, EN, z.e_head)) ||
+        (rc = reserve_group(ctx, c.st, "e_pick", z.lc_cap, 1024, EN, z.e_pick)) ||
+        (rc = reserve_group(ctx, c.st, "r_orig, r_w", z.lr_cap, 1024, lb.n_lb, z.r_orig, z.r_w)) ||
+        (rc = reserve_group(ctx, c.st, "p_key..p_hwm", z.k_cap, 1024, N, z.p_key, z.p_rank, z.p_hwm)))
+        return rc;
+    ZRESERVE(ctx, z.x_tot, grown_cap(z.x_tot.count, 1024, D), c.st);
+    if ((rc = forward_receive(ctx, c)))
+        return rc;
+    if (N == 0) {
+        if (G > 0) {
+            hipLaunchKernelGGL(k_fwd_lb_groups, dim3(wave_grid(G, kFwdThreads)), dim3(kFwdThreads), 0, c.st,
+                               (uint32_t) G, gidx, gstr, nullptr, lb.grp_idx, (uint32_t) lb.n_lb, lb.lb_cur,
+                               z.s_first.p);
+            ZCHECK(ctx, hipGetLastError());
+        }
+        if (D > 0) {
+            ZCHECK(ctx, hipMemsetAsync(cr.dst_taken, 0, 4 * (size_t) D, c.st));
+            ZCHECK(ctx, hipMemsetAsync(cr.dst_dropped, 0, 4 * (size_t) D, c.st));
+        }
+        return 0;
+    }
+    // (N > 0: forward_begin has seen to n_dst > 0)
+    ZCHECK(ctx, hipMemsetAsync(z.x_tot.p, 0, 4 * (size_t) D, c.st));
+    hipLaunchKernelGGL(k_fwd_heads<true>, dim3(wave_grid(S, kFwdThreads)), dim3(kFwdThreads), 0, c.st, c.src, c.tab,
+                       z.e_head.p, z.e_rank.p, z.s_msgs.p);
+    ZCHECK(ctx, hipGetLastError());
+    if (G > 0) {
+        hipLaunchKernelGGL(k_fwd_lb_credit_groups, dim3((unsigned) G), dim3(kFwdThreads), 0, c.st, gidx, gstr,
+                           (const uint32_t *) z.s_msgs.p, (const uint32_t *) c.tab.ebase, lb.grp_idx,
+                           (uint32_t) lb.n_lb, lb.lb_dst, D, (const uint32_t *) cr.dst_credit, lb.lb_cur, z.s_first.p,
+                           z.r_orig.p, z.r_w.p, z.e_pick.p, z.x_tot.p);
+        ZCHECK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_fwd_pairs_lb_credit, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, c.st, (uint32_t) N,
+                       c.src, c.tab, lb.flags & ZMQG_LB_PREPEND, sgrp, z.e_head.p, z.e_rank.p,
+                       (const uint32_t *) z.e_pick.p, lb.grp_idx, (uint32_t) lb.n_lb, lb.src_id_off, lb.src_id_len,
+                       c.out, lb.dest_out, z.p_hwm.p);
+    ZCHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fwd_credit_totals, dim3((D + 255) / 256), dim3(256), 0, c.st, D,
+                       (const uint32_t *) z.x_tot.p, cr.dst_credit, cr.dst_taken, cr.dst_dropped,
+                       cr.flags & ZMQG_CREDIT_CONSUME);
+    ZCHECK(ctx, hipGetLastError());
     return 0;
 }

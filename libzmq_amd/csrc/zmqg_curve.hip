@@ -3423,7 +3423,7 @@ static int forward_router(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zm
 // array of it the host can see.  grp_idx, lb_dst and lb_cur live on the device;
 // the kernels bound every read of them (curve_fwd_lb.hpp).
 static int forward_lb(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_lb *lb, const FwdFraming &fr,
-                      void *stream)
+                      void *stream, const zmqg_forward_credit *credit = nullptr)
 {
     if (!ctx || !args || !lb || lb->size != sizeof *lb || (lb->flags & ~ZMQG_LB_PREPEND) != 0)
         return -EINVAL;
@@ -3442,8 +3442,11 @@ static int forward_lb(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_f
     // one route slot a stream; PREPEND: an id slot in front of every element
     const FwdTableIn in = {args, true, true, lb->flags & ZMQG_LB_PREPEND ? 2u : 1u, lb->stream_group, lb->n_groups};
     FwdCall c;
+    c.credit = credit;
+    c.credit_in_plan = credit != nullptr; // (zmqg_forward_lb_credit_multi: lb_t's skip, made with the choice)
     int rc;
-    if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() || (rc = fwd_plan_lb(ctx, c, *lb)))
+    if ((rc = forward_begin(ctx, in, fr, stream, c)) || c.empty() ||
+        (rc = credit ? fwd_plan_lb_credit(ctx, c, *lb) : fwd_plan_lb(ctx, c, *lb)))
         return rc;
     return forward_finish(ctx, c);
 }
@@ -3491,8 +3494,8 @@ static int forward_framed(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zm
         return forward_sub(ctx, args, (const zmqg_forward_subs *) framing->plan, fr, stream, credit);
     case ZMQG_FWD_ROUTER:
         return forward_router(ctx, args, (const zmqg_forward_router *) framing->plan, fr, stream, credit);
-    case ZMQG_FWD_LB: // (no credit: zmqg_forward_credit_multi refuses the mode)
-        return forward_lb(ctx, args, (const zmqg_forward_lb *) framing->plan, fr, stream);
+    case ZMQG_FWD_LB: // (credit: zmqg_forward_lb_credit_multi's alone; zmqg_forward_credit_multi refuses the mode)
+        return forward_lb(ctx, args, (const zmqg_forward_lb *) framing->plan, fr, stream, credit);
     default:
         return forward_static(ctx, args, fr, stream, credit);
     }
@@ -3515,6 +3518,22 @@ int zmqg_forward_credit_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, cons
         (credit->flags & ~ZMQG_CREDIT_CONSUME) != 0)
         return -EINVAL;
     if (framing->size != sizeof *framing || framing->mode == ZMQG_FWD_LB || args->size != sizeof *args)
+        return -EINVAL;
+    if (args->n_dst > 0 && (!credit->dst_credit || !credit->dst_taken || !credit->dst_dropped))
+        return -EINVAL;
+    return forward_framed(ctx, args, framing, credit, stream);
+}
+
+// The credit struct's launch-free checks, then the framed load balancer with
+// the choice made under the credits (curve_fwd_lb_credit.hpp): lb_t takes a full
+// pipe out of the ring and gives the message to the next (src/lb.cpp:103-107).
+int zmqg_forward_lb_credit_multi(zmqg_ctx *ctx, const zmqg_forward_zmtp *args, const zmqg_forward_framing *framing,
+                                 const zmqg_forward_credit *credit, void *stream)
+{
+    if (!ctx || !args || !framing || !credit || credit->size != sizeof *credit ||
+        (credit->flags & ~ZMQG_CREDIT_CONSUME) != 0)
+        return -EINVAL;
+    if (framing->size != sizeof *framing || framing->mode != ZMQG_FWD_LB || args->size != sizeof *args)
         return -EINVAL;
     if (args->n_dst > 0 && (!credit->dst_credit || !credit->dst_taken || !credit->dst_dropped))
         return -EINVAL;

@@ -196,6 +196,8 @@ class ForwardCredit(ctypes.Structure):  # zmqg_forward_credit
 
 _lib.zmqg_forward_credit_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardFraming),
                                            ctypes.POINTER(ForwardCredit), _P]
+_lib.zmqg_forward_lb_credit_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardFraming),
+                                              ctypes.POINTER(ForwardCredit), _P]
 _lib.zmqg_forward_framed_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardFraming), _P]
 _lib.zmqg_forward_zmtp_lb_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), ctypes.POINTER(ForwardLb), _P]
 _lib.zmqg_forward_zmtp_multi.argtypes = [_P, ctypes.POINTER(ForwardZmtp), _P]
@@ -894,6 +896,32 @@ class CurveContext:
                            _ptr(dst_taken), _ptr(dst_dropped))
         self._check(_lib.zmqg_forward_credit_multi(self._ctx, ctypes.byref(a), ctypes.byref(fr), ctypes.byref(cr),
                                                    _stream_handle(stream)), "zmqg_forward_credit_multi")
+        del keep
+
+    def forward_lb_credit_multi(self, recv, send, dst_credit, dst_taken, dst_dropped, stream_sid, stream_off,
+                                stream_len, inp, max_msg_size, max_frames, frame_in_off, frame_len, plain_off, plain,
+                                flags_out, status_out, results, dst_sid, out, pair_off, pair_status, dst_results, fwd,
+                                consume=False, ws_results=None, mask=None, carry_idx=None, carry_off=None,
+                                carry_len=None, carry_flags=None, stream=None, out_bytes=None, **plan):
+        """forward_framed_multi with FWD_LB under a high-water mark per
+        destination (zmqg_forward_lb_credit_multi): a destination whose
+        credit has run out is taken out of its group's ring for the rest of the
+        call and the message goes to the next one, as lb_t does for a full
+        pipe; a message that finds the whole ring full is not sent, reports
+        ERR_HWM in pair_status and LB_NO_PEER in dest_out, and stays whole in
+        `plain` for a later call's carry.  dst_credit, dst_taken and
+        dst_dropped are forward_credit_multi's; the table arguments (flags,
+        stream_group, grp_idx, lb_dst, lb_cur, ...) are forward_zmtp_lb_multi's
+        as keywords.  lb_cur[g] is left at the original ring position the
+        cursor points at."""
+        a, fr, keep = self._framed_args(recv, send, FWD_LB, stream_sid, stream_off, stream_len, inp, max_msg_size,
+                                        max_frames, frame_in_off, frame_len, plain_off, plain, flags_out, status_out,
+                                        results, dst_sid, None, None, out, pair_off, pair_status, dst_results, fwd,
+                                        ws_results, mask, carry_idx, carry_off, carry_len, carry_flags, out_bytes, plan)
+        cr = ForwardCredit(ctypes.sizeof(ForwardCredit), CREDIT_CONSUME if consume else 0, _ptr(dst_credit),
+                           _ptr(dst_taken), _ptr(dst_dropped))
+        self._check(_lib.zmqg_forward_lb_credit_multi(self._ctx, ctypes.byref(a), ctypes.byref(fr), ctypes.byref(cr),
+                                                      _stream_handle(stream)), "zmqg_forward_lb_credit_multi")
         del keep
 
     @staticmethod
